@@ -497,7 +497,7 @@ def test_bench_rccl_world1():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(root, 'bench.py'),
            '--gpus', '1', '--steps', '6', '--warmup', '2', '--unique', '512', '--dataset-size', '40000',
-           '--no-cpu-baseline', '--no-later-epochs', '--no-c5', '--parity-rows', '256']
+           '--full', '--no-cpu-baseline', '--no-later-epochs', '--no-c5', '--parity-rows', '256']
     # the environment as the driver's run gets it (the box exports
     # HSA_ENABLE_IPC_MODE_LEGACY=0 itself; bench.py's self-launch keeps it)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=root)
@@ -521,8 +521,8 @@ def test_bench_gpus2_self_launch():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2',
-           '--unique', '512', '--dataset-size', '40000', '--no-cpu-baseline', '--no-later-epochs', '--no-c5',
-           '--parity-rows', '256']
+           '--unique', '512', '--dataset-size', '40000', '--full', '--no-cpu-baseline', '--no-later-epochs',
+           '--no-c5', '--parity-rows', '256']
     env = dict(os.environ, FFCV_BENCH_BACKEND='gloo')
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -535,3 +535,39 @@ def test_bench_gpus2_self_launch():
     assert abs(line['value'] - 2 * 512 * 6 / max(p['seconds'] for p in pg['per_rank'])) < 0.01 * line['value']
     par = line['parity']
     assert par['checked_all_ranks'] > par['checked'] > 0 and par['mismatch_all_ranks'] == 0
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times its steps and nothing else:
+    the line has `value` and `ms_per_step` for exactly --steps steps and no
+    parity / later-epoch / CPU / sub-result records; --dump-outputs writes a
+    float32 sample of the last timed step's rows, the same from run to run
+    (the second run is the --full one, whose parity check is green)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '6', '--warmup', '2',
+            '--unique', '512', '--dataset-size', '40000']
+    lines, dumps = [], []
+    for i, extra in enumerate(([], ['--full', '--no-cpu-baseline', '--no-later-epochs', '--no-c5'])):
+        d = str(tmp_path / f'dump{i}')
+        r = subprocess.run(base + ['--dump-outputs', d] + extra, capture_output=True, text=True, timeout=110,
+                           cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]))
+        dumps.append({n: np.load(os.path.join(d, n)) for n in sorted(os.listdir(d))})
+    plain, full = lines
+    assert plain['steps'] == 6 and plain['value'] > 0
+    assert abs(plain['value'] - 512 * 1e3 / plain['ms_per_step']) < 0.01 * plain['value']
+    assert plain['cpu_baseline'] is None
+    assert not any(k in plain for k in ('parity', 'later_epochs', 'c5', 'c2', 'c1'))
+    assert 'per_kernel' not in plain['roofline']
+    assert full['parity']['checked'] > 0 and full['parity']['mismatch'] == 0
+    assert sorted(dumps[0]) == ['images.npy', 'rows.npy', 'sample_ids.npy']
+    img = dumps[0]['images.npy']
+    assert img.dtype == np.float32 and img.shape[1:] == (224, 224, 3) and img.shape[0] == len(dumps[0]['rows.npy'])
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 * 1000 * 1000
+    assert np.isfinite(img).all() and img.std() > 0
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

@@ -4,7 +4,7 @@
 #   tools/ab_args.sh <tag> <reps> "name=args" "name=args" ...
 #   e.g. tools/ab_args.sh sch 3 "base=" "k1s=--k1-streams 1 --split 8,8,4"
 TAG=$1; R=$2; shift 2
-BASE="--no-cpu-baseline --no-later-epochs --no-c5 --parity-rows 512 --steps 20 --warmup 5"
+BASE="--full --no-cpu-baseline --no-later-epochs --no-c5 --parity-rows 512 --steps 20 --warmup 5"
 mkdir -p gpurun_out
 for r in $(seq $R); do
   for set in "$@"; do

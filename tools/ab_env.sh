@@ -3,7 +3,7 @@
 # context is made, e.g. FFCV_K1_ORDER) on the C3 bench:
 #   tools/ab_env.sh <tag> <VAR> "<values>" <reps> [bench args]
 TAG=$1; VAR=$2; VALS=$3; R=$4; shift 4
-ARGS="--no-cpu-baseline --no-later-epochs --no-c5 --parity-rows 512 $@"
+ARGS="--full --no-cpu-baseline --no-later-epochs --no-c5 --parity-rows 512 $@"
 mkdir -p gpurun_out
 for r in $(seq $R); do
   for v in $VALS; do

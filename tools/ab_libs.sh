@@ -5,7 +5,7 @@
 # isolated ns per image from the line's per_kernel record.
 #   tools/ab_libs.sh "base new" <reps> [bench args]
 V=${1:-"base new"}; R=${2:-2}; shift 2
-ARGS="--no-cpu-baseline --no-later-epochs --no-c5 --parity-rows 256 $@"
+ARGS="--full --no-cpu-baseline --no-later-epochs --no-c5 --parity-rows 256 $@"
 mkdir -p gpurun_out
 for r in $(seq $R); do
   for v in $V; do

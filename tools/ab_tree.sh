@@ -4,7 +4,7 @@
 # name = the working tree with --lib build/ab/<name>.so:
 #   tools/ab_tree.sh "old new w4" <reps> [bench args]
 V=${1:-"old new"}; R=${2:-2}; shift 2
-ARGS="--no-cpu-baseline --no-later-epochs --parity-rows 256 $@"
+ARGS="--full --no-cpu-baseline --no-later-epochs --parity-rows 256 $@"
 for r in $(seq $R); do
   for v in $V; do
     d=.; lib=""

@@ -8,7 +8,7 @@ TAG=${1:-c5s}
 mkdir -p gpurun_out
 for b in 0.08,0.15 0.15,0.25 0.25,0.40 0.40,0.60 0.60,0.76 0.78,1.0; do
   f=gpurun_out/${TAG}_$b.log
-  timeout -k 10 300 python bench.py --config c5 --unique 1024 --steps 40 --warmup 10 --no-cpu-baseline --no-later-epochs --parity-rows 0 --inflight 1 --draw-scale $b > $f 2>&1 || { tail -3 $f; exit 1; }
+  timeout -k 10 300 python bench.py --full --config c5 --unique 1024 --steps 40 --warmup 10 --no-cpu-baseline --no-later-epochs --parity-rows 0 --inflight 1 --draw-scale $b > $f 2>&1 || { tail -3 $f; exit 1; }
   python3 - $f $b <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -7,17 +7,19 @@
 set -e
 TAG=${1:-r4a}; PART=${2:-all}
 mkdir -p gpurun_out
+OUT=${OUT:-evidence}   # where the benchmark lines go
+mkdir -p $OUT
 if [ $PART != prof ]; then
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread > gpurun_out/${TAG}_tests.log 2>&1
 tail -1 gpurun_out/${TAG}_tests.log
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver.log 2>&1
-timeout -k 10 300 python bench.py --no-c5 > gpurun_out/${TAG}_bench.log 2>&1
-timeout -k 10 300 python bench.py --config c5 --steps 200 --warmup 20 --unique 1024 > gpurun_out/${TAG}_bench_c5.log 2>&1
-timeout -k 10 300 python bench.py --config c2 --steps 200 --warmup 20 --unique 10000 > gpurun_out/${TAG}_bench_c2.log 2>&1
-timeout -k 10 300 python bench.py --entropy-index --no-cpu-baseline --no-c5 > gpurun_out/${TAG}_bench_eidx.log 2>&1
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver.log 2>&1
+timeout -k 10 300 python bench.py --full --no-c5 > $OUT/${TAG}_bench.log 2>&1
+timeout -k 10 300 python bench.py --full --config c5 --steps 200 --warmup 20 --unique 1024 > $OUT/${TAG}_bench_c5.log 2>&1
+timeout -k 10 300 python bench.py --full --config c2 --steps 200 --warmup 20 --unique 10000 > $OUT/${TAG}_bench_c2.log 2>&1
+timeout -k 10 300 python bench.py --full --entropy-index --no-cpu-baseline --no-c5 > $OUT/${TAG}_bench_eidx.log 2>&1
 # N > 1 rehearsal on one GPU: two ranks, gloo barrier (the driver's 8-GPU run uses RCCL)
-FFCV_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 40 --warmup 10 --no-cpu-baseline --no-later-epochs > gpurun_out/${TAG}_bench_2rank.log 2>&1
-for f in bench_driver bench bench_c5 bench_c2 bench_eidx bench_2rank; do tail -1 gpurun_out/${TAG}_$f.log | cut -c1-200; done
+FFCV_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 40 --warmup 10 --no-cpu-baseline --no-later-epochs > $OUT/${TAG}_bench_2rank.log 2>&1
+for f in bench_driver bench bench_c5 bench_c2 bench_eidx bench_2rank; do tail -1 $OUT/${TAG}_$f.log | cut -c1-200; done
 fi
 [ $PART = bench ] && { echo EVIDENCE_DONE; exit 0; }
 # every profiled launch the same size (C3 / C2: 24 batches per launch, warmup = one launch)
