@@ -159,7 +159,8 @@ FFCV_HD uint64_t splitmix64(uint64_t x) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-// Seeding contract: op ids 1 = crop, 2 = cutout, 3 = flip.
+// Seeding contract: op ids 1 = crop, 2 = cutout, 3 = flip,
+// 4 = translate.
 FFCV_HD uint32_t sample_seed(uint64_t loader_seed, uint64_t epoch, uint64_t sample, uint32_t op) {
   uint64_t h = splitmix64(loader_seed ^ ((uint64_t)op << 56));
   h = splitmix64(h ^ epoch);
@@ -252,6 +253,17 @@ FFCV_HD int draw_part(int part, int k, uint64_t id, uint32_t H, uint32_t W, cons
     flips[k] = (uint8_t)(mt_double(m) < p.flip_prob);
   }
   return 0;
+}
+
+// RandomTranslate's window of one sample (translate.py:40-41: y, then x, each
+// randint(0, 2 * padding + 1)) from the sample's own stream, op id 4 ->
+// yx[2k..].  Returns 1 when the MT19937 stream ran out (FFCV_SAMPLE_RNG).
+FFCV_HD int draw_translate(int k, uint64_t id, uint64_t loader_seed, uint64_t epoch, int padding, int32_t *yx) {
+  DevMT m;
+  mt_init(m, sample_seed(loader_seed, epoch, id, 4));
+  yx[2 * k + 0] = (int32_t)mt_randint(m, 2 * (int64_t)padding + 1);
+  yx[2 * k + 1] = (int32_t)mt_randint(m, 2 * (int64_t)padding + 1);
+  return m.err;
 }
 
 

@@ -212,6 +212,21 @@ int ffcv_draw_batch_host(const uint64_t *sample_ids, const uint32_t *heights, co
   return FFCV_OK;
 }
 
+int ffcv_translate_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch,
+                                   int padding, int32_t *yx) {
+  if (batch < 0 || !sample_ids || !yx || padding < 0 || padding >= (1 << 30)) {
+    ffcv::set_error("ffcv_translate_draw_batch_host: invalid arguments (padding %d)", padding);
+    return FFCV_EINVAL;
+  }
+  int err = 0;
+  for (int k = 0; k < batch; k++) err |= draw_translate(k, sample_ids[k], loader_seed, epoch, padding, yx);
+  if (err) {
+    ffcv::set_error("ffcv_translate_draw_batch_host: MT19937 stream exhausted");
+    return FFCV_EINVAL;
+  }
+  return FFCV_OK;
+}
+
 int ffcv_imdecode_device(unsigned char *input_buffer, uint64_t input_size, uint32_t source_height,
                          uint32_t source_width, unsigned char *output_buffer, uint32_t crop_height,
                          uint32_t crop_width, uint32_t offset_x, uint32_t offset_y, uint32_t scale_num,

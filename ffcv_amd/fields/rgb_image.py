@@ -5,7 +5,9 @@ reference, but the decoders run on the HIP device that the Loader feeds:
 
 * ``SimpleRGBImageDecoder`` (rgb_image.py:84-139): raw -> device gather,
   jpg -> full JPEG decode kernel; constant-size datasets only (TypeError
-  otherwise, as the reference).  Without a GPU (the reference's C1 CPU
+  otherwise, as the reference).  Raw samples followed by a chain that holds a
+  RandomTranslate (with flip / Cutout in any order, then NormalizeImage fp16)
+  run as ONE launch behind the draws (ffcv_simple_aug_batch).  Without a GPU (the reference's C1 CPU
   plumbing config) raw samples are copied on the host with ``my_memcpy``.
 * ``RandomResizedCropRGBImageDecoder`` / ``CenterCropRGBImageDecoder``
   (rgb_image.py:142-265): crop windows are drawn ON THE DEVICE under the
@@ -89,6 +91,24 @@ class SimpleRGBImageDecoder(Operation):
 
     def __init__(self):
         super().__init__()
+        self._fused_steps = ()
+        self._fused_normalize = None
+
+    # graph lowering hook: the flip / translate / cutout operations (in
+    # pipeline order) and the fp16 NormalizeImage that the small-image kernel
+    # (ffcv_simple_aug_batch) applies while it reads the raw samples
+    def fuse(self, steps=(), normalize=None):
+        self._fused_steps = tuple(steps)
+        self._fused_normalize = normalize if self._fused_steps else None
+
+    @property
+    def fused(self):
+        """True when the graph lowered this decoder's chain into one launch."""
+        return bool(self._fused_steps)
+
+    @property
+    def output_dtype(self):
+        return ch.float16 if self._fused_normalize is not None else ch.uint8
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, AllocationQuery]:
         widths = self.metadata['width']
@@ -105,6 +125,15 @@ instead."""
         self._has_jpg = bool((self.metadata['mode'] == IMAGE_MODES['jpg']).any())
         if dev.type == 'cuda':
             self._on_device = True
+            if self.fused:
+                return (replace(previous_state, jit_mode=False, device=dev, shape=biggest_shape,
+                                dtype=self.output_dtype),
+                        (AllocationQuery(biggest_shape, self.output_dtype, dev),
+                         AllocationQuery((32,), ch.uint8, dev),    # ffcv_sample descriptor
+                         AllocationQuery((1,), ch.int32, dev),     # decode status
+                         AllocationQuery((2,), ch.int32, dev),     # translate window
+                         AllocationQuery((2,), ch.int32, dev),     # cutout origin
+                         AllocationQuery((1,), ch.uint8, dev)))    # flip decision
             return (replace(previous_state, jit_mode=False, device=dev, shape=biggest_shape,
                             dtype=ch.uint8),
                     (AllocationQuery(biggest_shape, ch.uint8, dev),
@@ -160,6 +189,8 @@ instead."""
             return decode_host
 
         f_ix = self._field_index
+        if self.fused:
+            return self._generate_code_fused(f_ix)
 
         def decode(batch_indices, storage, metadata, ss):
             out, smp, status = storage
@@ -173,6 +204,65 @@ instead."""
                 dec = ss.jpeg_decoder(f_ix)
                 dec.decode(ss.data, samples, B, out, stride, status, stream)
                 ss.check_status(status[:B], 'SimpleRGBImageDecoder')
+            return out[:B]
+        return decode
+
+    def _generate_code_fused(self, f_ix) -> Callable:
+        """Raw samples through flip / translate / cutout (+ fp16 LUT) in one
+        launch behind the draws (ffcv_simple_aug_batch): each sample is read
+        once from the .beton bytes and its final pixels are written once."""
+        from .. import libffcv as L
+        from ..transforms import Cutout, RandomHorizontalFlip, RandomTranslate
+        ap = L.SimpleAugParams()
+        ap.n_steps = len(self._fused_steps)
+        flip = cut = tr = None
+        for i, op in enumerate(self._fused_steps):
+            if isinstance(op, RandomHorizontalFlip):
+                ap.steps[i], flip = L.AUG_FLIP, op
+            elif isinstance(op, RandomTranslate):
+                ap.steps[i], tr = L.AUG_TRANSLATE, op
+                ap.padding = int(op.padding)
+                for c, v in enumerate(op.fill_u8()):
+                    ap.translate_fill[c] = int(v)
+            elif isinstance(op, Cutout):
+                ap.steps[i], cut = L.AUG_CUTOUT, op
+                ap.cutout_size = int(op.crop_size)
+                fill = np.broadcast_to(np.asarray(op.fill).astype(np.uint8).reshape(-1), (3,))
+                for c in range(3):
+                    ap.cutout_fill[c] = int(fill[c])
+            else:
+                raise TypeError(f'{type(op).__name__} cannot be fused into SimpleRGBImageDecoder')
+        norm = self._fused_normalize
+
+        def draw_params(ss, H, W):
+            key = (int(ss.loader_seed), int(ss.epoch), H, W)
+            cached = getattr(self, '_dp_cache', None)
+            if cached is not None and cached[0] == key:
+                return cached[1]
+            p = L.DrawParams()
+            p.out_h, p.out_w = H, W
+            p.cutout_size = int(cut.crop_size) if cut is not None else 0
+            p.flip_prob = float(flip.flip_prob) if flip is not None else 0.0
+            p.loader_seed = int(ss.loader_seed) & 0xFFFFFFFFFFFFFFFF
+            p.epoch = int(ss.epoch)
+            self._dp_cache = (key, p)
+            return p
+
+        def decode(batch_indices, storage, metadata, ss):
+            out, smp, status, tyx, cyx, flips = storage
+            B = len(batch_indices)
+            stream = ss.stream
+            H, W = int(out.shape[1]), int(out.shape[2])
+            samples = ss.batch_samples(f_ix, smp)
+            if flip is not None or cut is not None:
+                L.draw_batch(ss.batch_ids, None, draw_params(ss, H, W), None, cyx if cut is not None else None,
+                             flips if flip is not None else None, None, stream)
+            if tr is not None:
+                L.translate_draw_batch(ss.batch_ids, ss.loader_seed, ss.epoch, ap.padding, tyx, None, stream)
+            L.simple_aug_batch(ss.data, samples, B, H, W, ap, flips if flip is not None else None,
+                               cyx if cut is not None else None, tyx if tr is not None else None,
+                               norm.device_lut(out.device) if norm is not None else None, out,
+                               out[0].numel() * out.element_size(), stream)
             return out[:B]
         return decode
 

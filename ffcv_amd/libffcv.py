@@ -60,6 +60,16 @@ class DrawParams(ctypes.Structure):
                 ('flip_prob', ctypes.c_double)]
 
 
+# ffcv_simple_aug_params steps (FFCV_AUG_*)
+AUG_FLIP, AUG_TRANSLATE, AUG_CUTOUT = 1, 2, 3
+
+
+class SimpleAugParams(ctypes.Structure):
+    _fields_ = [('n_steps', c_int32), ('steps', ctypes.c_uint8 * 4), ('padding', c_int32),
+                ('cutout_size', c_int32), ('translate_fill', ctypes.c_uint8 * 4),
+                ('cutout_fill', ctypes.c_uint8 * 4)]
+
+
 _lib = None
 
 _SIGS = {
@@ -118,6 +128,13 @@ _SIGS = {
     'ffcv_lut_batch': (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_void_p]),
     'ffcv_flip_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                 c_void_p]),
+    'ffcv_translate_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_void_p,
+                                          c_void_p]),
+    'ffcv_translate_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_void_p]),
+    'ffcv_translate_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                     c_void_p]),
+    'ffcv_simple_aug_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -374,6 +391,40 @@ def flip_batch(inp, out, flips, stream=None):
     cb = int(inp[0, 0, 0].numel() * inp.element_size())
     _check(lib().ffcv_flip_batch(_stream(stream), _p(inp), _p(out), B, H, W, cb, _p(flips)),
            'ffcv_flip_batch')
+
+
+def translate_draw_batch(ids, loader_seed, epoch, padding, yx, status=None, stream=None):
+    """RandomTranslate windows (y, x) of the batch on the device (op id 4)."""
+    _check(lib().ffcv_translate_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                           int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(padding),
+                                           _p(yx), _p(status)), 'ffcv_translate_draw_batch')
+
+
+def translate_draw_batch_host(ids, loader_seed, epoch, padding):
+    """The same draws on the host: int32 (B, 2) of (y, x)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    yx = np.empty((ids.size, 2), np.int32)
+    _check(lib().ffcv_translate_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+                                                int(epoch), int(padding), _p(yx)),
+           'ffcv_translate_draw_batch_host')
+    return yx
+
+
+def translate_batch(inp, out, yx, padding, fill, stream=None):
+    B, H, W = int(inp.shape[0]), int(inp.shape[1]), int(inp.shape[2])
+    f = (ctypes.c_uint8 * 3)(*[int(x) for x in fill])
+    _check(lib().ffcv_translate_batch(_stream(stream), _p(inp), _p(out), B, H, W, _p(yx), int(padding), f),
+           'ffcv_translate_batch')
+
+
+def simple_aug_batch(base, samples, batch, height, width, params: SimpleAugParams, flips, cutout_yx,
+                     translate_yx, lut, out, out_stride=0, stream=None):
+    """Raw constant-size samples -> flip / translate / cutout in the program's
+    order (+ fp16 LUT) in one launch (ffcv_simple_aug_batch)."""
+    _check(lib().ffcv_simple_aug_batch(_stream(stream), _p(base), _p(samples), int(batch), int(height),
+                                       int(width), ctypes.byref(params), _p(flips), _p(cutout_yx),
+                                       _p(translate_yx), _p(lut), _p(out), int(out_stride)),
+           'ffcv_simple_aug_batch')
 
 
 def scratch_bound(heights, widths, nbytes):

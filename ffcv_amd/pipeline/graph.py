@@ -10,7 +10,11 @@ stages and generates stage functions with ``ast``.  Here:
    followed (through ToTensor / ToDevice / ToTorchImage) by Cutout,
    RandomHorizontalFlip and NormalizeImage(float16) becomes ONE device launch
    (crop draws + decode + resize + epilogue); the absorbed operations keep
-   their state declarations but run as identities.
+   their state declarations but run as identities.  A plain
+   SimpleRGBImageDecoder of raw samples followed by a chain that contains
+   RandomTranslate (with RandomHorizontalFlip / Cutout in any order, then
+   NormalizeImage(float16)) is lowered the same way into the small-image
+   launch (``_lower_simple``).
 3. ``collect_requirements`` walks states exactly like graph.py:295-354.  A
    non-device-aware (user) operation that would receive device data gets an
    implicit device->host transfer in front of it, so reference-style numpy
@@ -144,12 +148,15 @@ class Graph:
 
     # ------------------------------------------------------------ fusion --
     def lower(self):
-        from ..fields.rgb_image import ResizedCropRGBImageDecoder
+        from ..fields.rgb_image import ResizedCropRGBImageDecoder, SimpleRGBImageDecoder
         from ..transforms import (Cutout, RandomHorizontalFlip, NormalizeImage, ToTensor, ToDevice,
                                   ToTorchImage)
         if self.device.type != 'cuda':
             return
         for name, chain in self._chains.items():
+            if chain and type(chain[0]) is SimpleRGBImageDecoder:
+                self._lower_simple(chain)
+                continue
             if not chain or not isinstance(chain[0], ResizedCropRGBImageDecoder):
                 continue
             dec = chain[0]
@@ -186,6 +193,49 @@ class Graph:
                     op._absorbed = True
                 break
             dec.fuse(cutout=cutout, flip=flip, cutout_before_flip=cut_before_flip, normalize=norm)
+
+    def _lower_simple(self, chain):
+        """A plain SimpleRGBImageDecoder of raw samples followed (through
+        ToTensor / ToDevice / ToTorchImage) by RandomHorizontalFlip,
+        RandomTranslate and Cutout in any order, each at most once, and then
+        optionally NormalizeImage(float16): ONE device launch behind the draws
+        (ffcv_simple_aug_batch).  Only chains that contain a RandomTranslate
+        are lowered; every other Simple-decoder chain, and any field with a
+        JPEG-mode sample, keeps its staged launches."""
+        from ..transforms import (Cutout, RandomHorizontalFlip, RandomTranslate, NormalizeImage, ToTensor,
+                                  ToDevice, ToTorchImage)
+        dec = chain[0]
+        steps, norm = [], None
+        layout_changed = False
+        for op in chain[1:]:
+            if len(self.operation_to_node[op]) != 1:
+                break
+            if isinstance(op, ToTensor):
+                continue
+            if isinstance(op, ToTorchImage):
+                layout_changed = True
+                continue
+            if isinstance(op, ToDevice):
+                t = ch.device(op.device)
+                if t.type == 'cuda' and (t.index is None or t.index == (self.device.index or 0)):
+                    continue
+                break
+            if isinstance(op, (Cutout, RandomHorizontalFlip, RandomTranslate)) and norm is None \
+                    and not layout_changed and not any(type(s) is type(op) for s in steps):
+                steps.append(op)
+                continue
+            if isinstance(op, NormalizeImage) and norm is None and \
+                    np.dtype(op.original_dtype) == np.float16 and \
+                    np.asarray(op.lookup_table).shape == (256, 3):
+                norm = op
+            break
+        fix = self.operation_to_node[dec][0].f_ix
+        has_jpg = bool((self.metadata[f'f{fix}']['mode'] == 0).any())
+        if has_jpg or not any(isinstance(s, RandomTranslate) for s in steps):
+            return
+        for op in steps + ([norm] if norm is not None else []):
+            op._absorbed = True
+        dec.fuse(steps=steps, normalize=norm)
 
     # ------------------------------------------------------ requirements --
     def _prepare(self, node: Node, op: Operation):

@@ -370,6 +370,67 @@ int ffcv_flip_batch(void *stream, const uint8_t *in, uint8_t *out, int batch,
                     int height, int width, int channels_bytes,
                     const uint8_t *flips);
 
+/* ------------------------------------------------- RandomTranslate ---- */
+/* translate.py:35-44: the image sits at offset `padding` in a canvas of
+ * `fill` sized (H + 2p, W + 2p); y = randint(0, 2p + 1) is drawn first,
+ * then x, and the output is the H x W window at (y, x):
+ *   out[r, c] = in[r + y - p, c + x - p] inside the image, else fill.
+ * Draws under the seeding contract with op id 4 (one lane per sample):
+ *   sample_ids : device uint64[B]
+ *   yx         : device int32[B][2] out (y, x)
+ *   status     : device int32[B] out (FFCV_SAMPLE_RNG when the sample's
+ *                MT19937 stream ran out), or NULL */
+int ffcv_translate_draw_batch(void *stream, const uint64_t *sample_ids,
+                              int batch, uint64_t loader_seed, uint64_t epoch,
+                              int padding, int32_t *yx, int32_t *status);
+/* The same draws on host arrays (the CPU-device Loader). */
+int ffcv_translate_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                   uint64_t loader_seed, uint64_t epoch,
+                                   int padding, int32_t *yx);
+/* Standalone translate of a device [B][H][W][3] uint8 batch into `out`
+ * (same shape; in == out is FFCV_EINVAL: shifted reads overlap the writes). */
+int ffcv_translate_batch(void *stream, const uint8_t *in, uint8_t *out,
+                         int batch, int height, int width, const int32_t *yx,
+                         int padding, const uint8_t fill[3]);
+
+/* ------------------------------- fused small-image augmentation ------- */
+/* Geometric steps of ffcv_simple_aug_batch's program. */
+enum {
+  FFCV_AUG_FLIP = 1,      /* flip.py:35-40, decided by flips[k] */
+  FFCV_AUG_TRANSLATE = 2, /* translate.py:35-44, window translate_yx[k] */
+  FFCV_AUG_CUTOUT = 3     /* cutout.py:36-47, square at cutout_yx[k] */
+};
+
+typedef struct ffcv_simple_aug_params {
+  int32_t n_steps;           /* 1..3 */
+  uint8_t steps[4];          /* FFCV_AUG_* in pipeline order, each at most once */
+  int32_t padding;           /* RandomTranslate padding */
+  int32_t cutout_size;       /* Cutout crop_size */
+  uint8_t translate_fill[4]; /* RGB ([3] unused) */
+  uint8_t cutout_fill[4];    /* RGB ([3] unused) */
+} ffcv_simple_aug_params;
+
+/* SimpleRGBImageDecoder raw branch (rgb_image.py:123-136) fused with
+ * RandomHorizontalFlip / RandomTranslate / Cutout in any order and the
+ * NormalizeImage LUT (normalize.py:65): one read of each raw sample, one
+ * write of the final pixels.  Every sample is height x width x 3 raw bytes
+ * at base + samples[k].offset (any byte alignment); samples of another mode
+ * or with fewer bytes are skipped.  Each output pixel walks the program
+ * backwards to the source pixel it shows (or to a fill colour), so every
+ * ordering of the steps gives what the separate operations give.
+ *   flips        : device uint8[B]      (required by a FLIP step, else NULL)
+ *   cutout_yx    : device int32[B][2]   (required by a CUTOUT step)
+ *   translate_yx : device int32[B][2]   (required by a TRANSLATE step)
+ *   lut          : device [256][3] fp16 bits, or NULL for uint8 output
+ *   out          : device [B][height][width][3] uint8 or fp16 bits,
+ *                  out_stride bytes per sample (0 = dense) */
+int ffcv_simple_aug_batch(void *stream, const uint8_t *base,
+                          const ffcv_sample *samples, int batch, int height,
+                          int width, const ffcv_simple_aug_params *p,
+                          const uint8_t *flips, const int32_t *cutout_yx,
+                          const int32_t *translate_yx, const uint16_t *lut,
+                          void *out, uint64_t out_stride);
+
 #ifdef __cplusplus
 }
 #endif
