@@ -160,7 +160,7 @@ FFCV_HD uint64_t splitmix64(uint64_t x) {
   return z ^ (z >> 31);
 }
 // Seeding contract: op ids 1 = crop, 2 = cutout, 3 = flip,
-// 4 = translate.
+// 4 = translate, 5 / 6 / 7 = brightness / contrast / saturation (color_common.h).
 FFCV_HD uint32_t sample_seed(uint64_t loader_seed, uint64_t epoch, uint64_t sample, uint32_t op) {
   uint64_t h = splitmix64(loader_seed ^ ((uint64_t)op << 56));
   h = splitmix64(h ^ epoch);

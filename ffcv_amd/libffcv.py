@@ -24,6 +24,7 @@ c_int = ctypes.c_int
 c_int32 = ctypes.c_int32
 c_uint32 = ctypes.c_uint32
 c_uint64 = ctypes.c_uint64
+c_double = ctypes.c_double
 
 # per-sample device status codes (FFCV_SAMPLE_*)
 SAMPLE_STATUS = {0: 'ok', 1: 'bad marker', 2: 'unsupported JPEG feature',
@@ -68,6 +69,11 @@ class SimpleAugParams(ctypes.Structure):
     _fields_ = [('n_steps', c_int32), ('steps', ctypes.c_uint8 * 4), ('padding', c_int32),
                 ('cutout_size', c_int32), ('translate_fill', ctypes.c_uint8 * 4),
                 ('cutout_fill', ctypes.c_uint8 * 4)]
+
+
+class ColorJitterParams(ctypes.Structure):
+    """ffcv_color_jitter_params: FFCV_CJ_* kinds in pipeline order."""
+    _fields_ = [('n_steps', c_int32), ('steps', ctypes.c_uint8 * 4)]
 
 
 _lib = None
@@ -135,6 +141,15 @@ _SIGS = {
                                      c_void_p]),
     'ffcv_simple_aug_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
+    'ffcv_color_jitter_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_double,
+                                             c_double, c_void_p, c_void_p, c_void_p]),
+    'ffcv_color_jitter_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_double, c_double,
+                                                  c_void_p, c_void_p]),
+    'ffcv_color_jitter_workspace_bytes': (c_uint64, [c_int]),
+    'ffcv_color_jitter_lds_bytes': (c_uint64, []),
+    'ffcv_color_jitter_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_uint64]),
+    'ffcv_color_jitter_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -425,6 +440,73 @@ def simple_aug_batch(base, samples, batch, height, width, params: SimpleAugParam
                                        int(width), ctypes.byref(params), _p(flips), _p(cutout_yx),
                                        _p(translate_yx), _p(lut), _p(out), int(out_stride)),
            'ffcv_simple_aug_batch')
+
+
+CJ_BRIGHTNESS, CJ_CONTRAST, CJ_SATURATION = 1, 2, 3
+
+
+def color_jitter_params(steps) -> ColorJitterParams:
+    """The program of FFCV_CJ_* kinds in pipeline order."""
+    p = ColorJitterParams()
+    p.n_steps = len(steps)
+    for i, st in enumerate(list(steps)[:4]):
+        p.steps[i] = int(st)
+    return p
+
+
+def color_jitter_draw_batch(ids, loader_seed, epoch, op_id, p, magnitude, apply, ratio, status=None, stream=None):
+    """Colour-jitter decisions of the batch on the device: apply uint8[B],
+    ratio float64[B] (op id 5 brightness, 6 contrast, 7 saturation)."""
+    _check(lib().ffcv_color_jitter_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                              int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(op_id),
+                                              float(p), float(magnitude), _p(apply), _p(ratio), _p(status)),
+           'ffcv_color_jitter_draw_batch')
+
+
+def color_jitter_draw_batch_host(ids, loader_seed, epoch, op_id, p, magnitude):
+    """The same draws on the host: (apply uint8 (B,), ratio float64 (B,))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    apply = np.empty(ids.size, np.uint8)
+    ratio = np.empty(ids.size, np.float64)
+    _check(lib().ffcv_color_jitter_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+                                                   int(epoch), int(op_id), float(p), float(magnitude), _p(apply),
+                                                   _p(ratio)), 'ffcv_color_jitter_draw_batch_host')
+    return apply, ratio
+
+
+def color_jitter_workspace_bytes(batch):
+    return int(lib().ffcv_color_jitter_workspace_bytes(int(batch)))
+
+
+def color_jitter_lds_bytes():
+    return int(lib().ffcv_color_jitter_lds_bytes())
+
+
+def color_jitter_batch(images, steps, apply, ratio, workspace=None, stream=None):
+    """The program ``steps`` in place on a device uint8 (B, H, W, 3) batch
+    (apply uint8 (n, B), ratio float64 (n, B)); one launch while an image fits
+    color_jitter_lds_bytes(), else one without and two with a contrast step."""
+    if images.dim() != 4 or int(images.shape[3]) != 3 or images.element_size() != 1 or not images.is_contiguous():
+        raise TypeError('color_jitter_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
+    B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    params = steps if isinstance(steps, ColorJitterParams) else color_jitter_params(steps)
+    wb = int(workspace.numel() * workspace.element_size()) if workspace is not None else 0
+    _check(lib().ffcv_color_jitter_batch(_stream(stream), _p(images), B, H, W, ctypes.byref(params), _p(apply),
+                                         _p(ratio), _p(workspace), wb), 'ffcv_color_jitter_batch')
+
+
+def color_jitter_batch_host(images, steps, apply, ratio):
+    """The same program in place on a C-contiguous numpy uint8 (B, H, W, 3)."""
+    if not (isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.flags.c_contiguous
+            and images.ndim == 4 and images.shape[3] == 3):
+        raise TypeError('color_jitter_batch_host: a C-contiguous uint8 (B, H, W, 3) array is required')
+    B, H, W = (int(x) for x in images.shape[:3])
+    params = steps if isinstance(steps, ColorJitterParams) else color_jitter_params(steps)
+    apply = np.ascontiguousarray(apply, np.uint8).reshape(params.n_steps, B)
+    ratio = np.ascontiguousarray(ratio, np.float64).reshape(params.n_steps, B)
+    _check(lib().ffcv_color_jitter_batch_host(_p(images), B, H, W, ctypes.byref(params), _p(apply), _p(ratio)),
+           'ffcv_color_jitter_batch_host')
+    return images
 
 
 def scratch_bound(heights, widths, nbytes):

@@ -14,7 +14,8 @@ stages and generates stage functions with ``ast``.  Here:
    SimpleRGBImageDecoder of raw samples followed by a chain that contains
    RandomTranslate (with RandomHorizontalFlip / Cutout in any order, then
    NormalizeImage(float16)) is lowered the same way into the small-image
-   launch (``_lower_simple``).
+   launch (``_lower_simple``).  A run of adjacent colour-jitter operations
+   becomes one launch of its own (``_lower_color``).
 3. ``collect_requirements`` walks states exactly like graph.py:295-354.  A
    non-device-aware (user) operation that would receive device data gets an
    implicit device->host transfer in front of it, so reference-style numpy
@@ -153,6 +154,8 @@ class Graph:
                                   ToTorchImage)
         if self.device.type != 'cuda':
             return
+        for chain in self._chains.values():
+            self._lower_color(chain)
         for name, chain in self._chains.items():
             if chain and type(chain[0]) is SimpleRGBImageDecoder:
                 self._lower_simple(chain)
@@ -236,6 +239,26 @@ class Graph:
         for op in steps + ([norm] if norm is not None else []):
             op._absorbed = True
         dec.fuse(steps=steps, normalize=norm)
+
+    def _lower_color(self, chain):
+        """A run of adjacent RandomBrightness / RandomContrast /
+        RandomSaturation, each kind at most once: ONE device launch behind
+        the draws (ffcv_color_jitter_batch).  The first operation of the run
+        carries the program, the others run as identities; a repeated kind
+        starts a new run.  (To the decoder lowerings a colour-jitter
+        operation is an unknown operation: it ends the fused prefix.)"""
+        from ..transforms.color_jitter import _ColorJitter
+        run = []
+        for op in chain:
+            if not isinstance(op, _ColorJitter) or len(self.operation_to_node[op]) != 1:
+                run = []
+                continue
+            if any(type(o) is type(op) for o in run):
+                run = []
+            run.append(op)
+            if len(run) > 1:
+                op._absorbed = True
+                run[0]._program = list(run)
 
     # ------------------------------------------------------ requirements --
     def _prepare(self, node: Node, op: Operation):

@@ -1,0 +1,188 @@
+"""RandomBrightness, RandomContrast, RandomSaturation
+(ffcv/transforms/color_jitter.py:16-139).
+
+Each operation draws ``rand() < p`` and then ``uniform(max(0, 1 - magnitude),
+1 + magnitude)`` from the sample's own MT19937 under the seeding contract
+(op id 5 brightness, 6 contrast, 7 saturation) and, where the first
+draw says so, blends the uint8 HWC image in float64 like the reference:
+``uint8(clip(ratio * v + (1 - ratio) * other, 0, 255))`` with ``other`` 0
+(brightness), the mean of the image's uint8 gray values (contrast) or the
+pixel's own gray value (saturation).
+
+On device tensors a run of adjacent colour-jitter operations is ONE
+ffcv_color_jitter_batch launch behind its draws (the graph lowering makes the
+first operation of the run carry the program); on host arrays each operation
+runs the numpy statement below, in place.
+"""
+import math
+from dataclasses import replace
+from typing import Callable, Optional, Tuple
+
+import numpy as np
+import torch as ch
+
+from ..pipeline.allocation_query import AllocationQuery
+from ..pipeline.operation import Operation
+from ..pipeline.state import State
+from ..pipeline import runtime
+from .rng import contract_seed
+
+_IDENT = np.arange(256, dtype=np.float64)
+
+
+def gray_u8(image):
+    """color_jitter.py:85: (0.2989 r + 0.587 g + 0.114 b).astype(uint8)."""
+    r, g, b = image[..., 0], image[..., 1], image[..., 2]
+    return (0.2989 * r + 0.587 * g + 0.114 * b).astype(np.uint8)
+
+
+def _table(ratio, other):
+    """blend() of every uint8 value against the scalar ``other``."""
+    return (ratio * _IDENT + (1 - ratio) * other).clip(0, 255).astype(np.uint8)
+
+
+def brightness_np(image, ratio):
+    """In place on one uint8 (H, W, 3) image."""
+    image[...] = _table(ratio, 0)[image]
+    return image
+
+
+def contrast_np(image, ratio):
+    gray = gray_u8(image)
+    mean = np.float64(int(gray.sum(dtype=np.int64))) / np.float64(gray.size)
+    image[...] = _table(ratio, mean)[image]
+    return image
+
+
+def saturation_np(image, ratio):
+    gray = gray_u8(image)
+    image[...] = (ratio * image + (1 - ratio) * gray[..., None]).clip(0, 255).astype(np.uint8)
+    return image
+
+
+def jitter_range(magnitude):
+    return max(0, 1 - magnitude), 1 + magnitude
+
+
+def jitter_draw(seed, epoch, sample, op_id, p, magnitude):
+    """(apply, ratio) of one sample under the seeding contract."""
+    rs = np.random.RandomState(contract_seed(seed, epoch, int(sample), op_id))
+    apply = bool(rs.rand() < p)
+    lo, hi = jitter_range(magnitude)
+    return apply, np.float64(rs.uniform(lo, hi))
+
+
+class _ColorJitter(Operation):
+    device_aware = True
+    per_sample = True
+    op_id = 0      # seeding-contract op id
+    kind = 0       # FFCV_CJ_*
+    host_fn = None
+
+    def __init__(self, magnitude: float, p=0.5):
+        super().__init__()
+        name = type(self).__name__
+        try:
+            m, pf = float(magnitude), float(p)
+        except (TypeError, ValueError):
+            raise ValueError(f'{name}: magnitude and p must be numbers, got {magnitude!r}, {p!r}')
+        if not math.isfinite(m) or m < 0:
+            raise ValueError(f'{name}: magnitude must be finite and >= 0, got {magnitude!r}')
+        if not 0 <= pf <= 1:
+            raise ValueError(f'{name}: p must lie in [0, 1], got {p!r}')
+        self.magnitude = magnitude
+        self.p = p
+        self._absorbed = False
+        self._program = [self]  # the run this operation leads (graph lowering)
+
+    def generate_code(self) -> Callable:
+        if self._absorbed:
+            def fused(images, *_):
+                return images
+            return fused
+        program = list(self._program)
+
+        def color_jitter(images, dst, indices):
+            ctx = runtime.current()
+            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
+                from .. import libffcv as L
+                B, n = int(images.shape[0]), len(program)
+                apply = ch.empty((n, B), dtype=ch.uint8, device=images.device)
+                ratio = ch.empty((n, B), dtype=ch.float64, device=images.device)
+                for i, op in enumerate(program):
+                    L.color_jitter_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, op.op_id, op.p,
+                                              op.magnitude, apply[i], ratio[i], None, ctx.stream)
+                ws = None
+                if int(images.shape[1]) * int(images.shape[2]) * 3 > L.color_jitter_lds_bytes() and \
+                        any(op.kind == L.CJ_CONTRAST for op in program):
+                    ws = ch.empty((B,), dtype=ch.int64, device=images.device)
+                L.color_jitter_batch(images, [op.kind for op in program], apply, ratio, ws, ctx.stream)
+                return images
+            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
+            arr = images.numpy() if isinstance(images, ch.Tensor) else images
+            for i, sid in enumerate(indices):
+                for op in program:
+                    apply, ratio = jitter_draw(seed, epoch, sid, op.op_id, op.p, op.magnitude)
+                    if apply:
+                        type(op).host_fn(arr[i], ratio)
+            return images
+        color_jitter.is_parallel = True
+        color_jitter.with_indices = True
+        return color_jitter
+
+    def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
+        dt, shape = previous_state.dtype, previous_state.shape
+        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
+        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
+            raise TypeError(f'{type(self).__name__} works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
+                            'place it before ToTorchImage / NormalizeImage / Convert')
+        return replace(previous_state, jit_mode=previous_state.device.type == 'cpu'
+                       and not isinstance(dt, ch.dtype)), None
+
+
+class RandomBrightness(_ColorJitter):
+    """Randomly adjust image brightness. Operates on raw arrays (not tensors).
+
+    Parameters
+    ----------
+    magnitude : float
+        randomly choose brightness enhancement factor on [max(0, 1-magnitude), 1+magnitude]
+    p : float
+        probability to apply brightness
+    """
+    op_id, kind, host_fn = 5, 1, staticmethod(brightness_np)
+
+    def __init__(self, magnitude: float, p=0.5):
+        super().__init__(magnitude, p)
+
+
+class RandomContrast(_ColorJitter):
+    """Randomly adjust image contrast. Operates on raw arrays (not tensors).
+
+    Parameters
+    ----------
+    magnitude : float
+        randomly choose contrast enhancement factor on [max(0, 1-magnitude), 1+magnitude]
+    p : float
+        probability to apply contrast
+    """
+    op_id, kind, host_fn = 6, 2, staticmethod(contrast_np)
+
+    def __init__(self, magnitude, p=0.5):
+        super().__init__(magnitude, p)
+
+
+class RandomSaturation(_ColorJitter):
+    """Randomly adjust image color balance. Operates on raw arrays (not tensors).
+
+    Parameters
+    ----------
+    magnitude : float
+        randomly choose color balance enhancement factor on [max(0, 1-magnitude), 1+magnitude]
+    p : float
+        probability to apply saturation
+    """
+    op_id, kind, host_fn = 7, 3, staticmethod(saturation_np)
+
+    def __init__(self, magnitude, p=0.5):
+        super().__init__(magnitude, p)

@@ -431,6 +431,72 @@ int ffcv_simple_aug_batch(void *stream, const uint8_t *base,
                           const int32_t *translate_yx, const uint16_t *lut,
                           void *out, uint64_t out_stride);
 
+/* ------------------------------------------------- colour jitter ------ */
+/* color_jitter.py: RandomBrightness / RandomContrast / RandomSaturation on
+ * uint8 HWC RGB images.  All arithmetic is float64, every multiply and add
+ * rounded on its own (never fused):
+ *   gray(r, g, b) = uint8(trunc((0.2989 r + 0.587 g) + 0.114 b))
+ *   blend(v, o)   = uint8(trunc(clip(ratio v + (1 - ratio) o, 0, 255)))
+ *   brightness: o = 0;  contrast: o = (sum of gray over the image) / (H W),
+ *   the same for the three channels;  saturation: o = gray(pixel).
+ * Draws under the seeding contract, one lane per sample, op_id 5 brightness,
+ * 6 contrast, 7 saturation: apply = rand() < p, then ratio = uniform(max(0,
+ * 1 - magnitude), 1 + magnitude); both are always drawn, in that order.
+ *   sample_ids : device uint64[B]
+ *   apply      : device uint8[B] out
+ *   ratio      : device float64[B] out
+ *   status     : device int32[B] out (FFCV_SAMPLE_RNG when the sample's
+ *                MT19937 stream ran out), or NULL */
+int ffcv_color_jitter_draw_batch(void *stream, const uint64_t *sample_ids,
+                                 int batch, uint64_t loader_seed,
+                                 uint64_t epoch, int op_id, double p,
+                                 double magnitude, uint8_t *apply,
+                                 double *ratio, int32_t *status);
+/* The same draws on host arrays (the CPU-device Loader). */
+int ffcv_color_jitter_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                      uint64_t loader_seed, uint64_t epoch,
+                                      int op_id, double p, double magnitude,
+                                      uint8_t *apply, double *ratio);
+
+enum {
+  FFCV_CJ_BRIGHTNESS = 1,
+  FFCV_CJ_CONTRAST = 2,
+  FFCV_CJ_SATURATION = 3
+};
+
+typedef struct ffcv_color_jitter_params {
+  int32_t n_steps;  /* 1..3 */
+  uint8_t steps[4]; /* FFCV_CJ_* in pipeline order, each at most once */
+} ffcv_color_jitter_params;
+
+/* Bytes of workspace ffcv_color_jitter_batch needs for `batch` images of any
+ * size and any program (one uint64 gray sum per image; only a program with a
+ * CONTRAST step on images beyond the one-workgroup regime uses it, every
+ * other call may pass NULL / 0). */
+uint64_t ffcv_color_jitter_workspace_bytes(int batch);
+/* The largest image (height * width * 3 bytes) one workgroup keeps in LDS:
+ * up to this size a program is ONE launch, beyond it one launch without and
+ * two launches with a CONTRAST step. */
+uint64_t ffcv_color_jitter_lds_bytes(void);
+/* The program in place on a device [B][height][width][3] uint8 batch; step
+ * i of image k runs when apply[i * batch + k] != 0, with ratio[i * batch +
+ * k], on the previous step's uint8 result, exactly as the separate
+ * operations would.  An image none of whose steps applies is not written.
+ *   apply : device uint8[n_steps][B];  ratio : device float64[n_steps][B]
+ *   workspace : device, 8-byte aligned, >= ffcv_color_jitter_workspace_bytes
+ *               (zeroed on the stream by the call), or NULL where unused */
+int ffcv_color_jitter_batch(void *stream, uint8_t *images, int batch,
+                            int height, int width,
+                            const ffcv_color_jitter_params *params,
+                            const uint8_t *apply, const double *ratio,
+                            void *workspace, uint64_t workspace_bytes);
+/* The same program on host memory, compiled from the same pixel functions
+ * as the kernels (gray, table entry, blend). */
+int ffcv_color_jitter_batch_host(uint8_t *images, int batch, int height,
+                                 int width,
+                                 const ffcv_color_jitter_params *params,
+                                 const uint8_t *apply, const double *ratio);
+
 #ifdef __cplusplus
 }
 #endif
