@@ -46,10 +46,12 @@
 //
 // K1b jpeg_idct_kernel -- one workgroup per image: DC prediction from the
 //   per-lane sums, de-zigzag + dequantise + ifast IDCT (jidctfst.c) of the
-//   window's blocks -> component planes in scratch.
+//   window's blocks -> component planes in scratch; K2's per-band records
+//   (K2BandRec: one thread per band).
 //
 // K2 jpeg_color_resize_kernel -- one workgroup per band of 16 output rows:
-//   stages the band's plane tiles and then its source rows of the crop as RGB
+//   reads the band's record (path, source rows, tiles, LDS layout), stages
+//   the band's plane tiles and then its source rows of the crop as RGB
 //   in LDS (jdsample.c fancy upsampling + jdcolor.c fixed-point YCbCr->RGB,
 //   once per source pixel), then computes the band's output pixels with the
 //   OpenCV 4.5.4 resize restatement (linear walk, area walk, or the general
@@ -166,6 +168,146 @@ struct ImgInfo {
 };
 
 #define K2_TAPS 512  // tap table entries per image: out_w + out_h <= 512 (tap_pack format)
+
+#ifndef K2_AREA_FAST
+#define K2_AREA_FAST 1  // 0: area crops take the general per-pixel path (A/B builds)
+#endif
+
+
+// K2's per-band record (RRC): everything a band workgroup of an OK image
+// needs once it has checked the image's status, written once per image by K1b
+// (one thread per band, from the image record it holds in LDS; JpegArgs::brec,
+// ceil(out_h / BAND) records per image)
+// instead of being rebuilt from ImgInfo by each of the image's band
+// workgroups (band_rows in f64, three components' tile bounds, the LDS layout
+// and the path selection: ~100 live scalars that spilled).  A band whose
+// selector is K2B_GENERAL reads nothing else of it: the general path keeps
+// the ImgInfo head.  Tile fields are packed in halves: a fast band's tile
+// rows, pitches and LDS offsets are below K2_LDS, plane and image dimensions
+// below 2^16 (ffcv_jpeg_create), strides multiples of 8 below 2^19.
+enum { K2B_GENERAL = 0, K2B_LINEAR = 1, K2B_AREA = 2 };  // fmt bits 0-1
+#define K2B_Q420 4u    // the 4:2:0 colour pass applies (every K2B_AREA band)
+#define K2B_TAPS 8u    // K1 wrote the image's linear tap table (ImgInfo::taps)
+#define K2B_NCOMP_SH 4     // bits 4-5: ncomp
+#define K2B_RGB 64u        // color_rgb
+#define K2B_EXP_SH 8       // from bit 8, per component c: log2 he at 4 c, log2 ve at 4 c + 2
+struct __attribute__((aligned(128))) K2BandRec {
+  uint32_t fmt;
+  int32_t r0, nrows;  // band_rows: crop rows [r0, r0 + nrows) feed this band
+  int32_t need;       // LDS bytes of the fast layout (fast selectors: <= K2_LDS)
+  uint64_t pbase[3];  // arena offset of tile sample (ty0, tx0): poff + ty0 * stride + tx0
+  uint32_t tyx[3];    // tile origin in the plane: ty0 | tx0 << 16
+  uint32_t trp[3];    // tile rows | tile pitch << 16
+  uint32_t tos[3];    // tile's LDS offset | (plane stride >> 3) << 16
+  uint32_t cwh[3];    // plane size: cw | ch << 16
+  uint32_t rgbp;      // LDS offset of the RGB rows | the area rows' pitch << 16
+  int32_t ri, rj, rw;
+  int32_t sw, sh;            // the plan's source size (the crop's)
+  double scale_x, scale_y;   // the plan's scales (the area walk's taps)
+};
+static_assert(sizeof(K2BandRec) == 128, "K2BandRec is 32 dwords");
+#define K2_REC_BANDS 16  // bands per image a context's record buffer starts with (out_h <= 256; grown on demand)
+
+// One band's record.  The expressions are the ones K2's set-up evaluated per
+// workgroup before (band_rows, the tile clamps and the LDS layout decide
+// which plane samples a band reads).  GS: the image's geometry (K1's LDS
+// state, or the image record), read where it is used and every field stored
+// as soon as it is known, so the writer adds nothing to its kernel's register
+// peak; the selector goes last (the layout's size decides it).  lut_b: bytes
+// of the FP16 LUT ahead of the layout.
+template <class GS>
+FFCV_DEV void k2_write_band_rec(K2BandRec *o, const GS &g, const ResizePlan &P, int out_w, int out_h, int band,
+                                int lut_b, int taps) {
+  // expansion factors 1 / 2 / 4 (every common subsampling): the tile bounds
+  // below divide by shifts; 3 takes the general path
+  auto p2 = [](int x) { return x == 1 || x == 2 || x == 4; };
+  const bool pow2 = p2(g.he(0)) && p2(g.ve(0)) && p2(g.he(1)) && p2(g.ve(1)) && p2(g.he(2)) && p2(g.ve(2));
+  const int ncomp = g.ncomp();
+  const bool q420 = ncomp == 3 && !g.color_rgb() && g.he(0) == 1 && g.ve(0) == 1 && g.he(1) == 2 && g.ve(1) == 2 &&
+                    g.he(2) == 2 && g.ve(2) == 2 && g.cw(1) > 2 && g.cw(2) > 2;
+  // area fast path (round 6): INTER_AREA crops with both scales in [1, 2)
+  // (every RRC crop larger than the output on both axes, up to 2x) of 4:2:0
+  // images.  (scale_x = 1 / (dw / sw) < 2 exactly when sw < 2 dw: integer
+  // tests keep the f64 scales out of this condition)
+  const bool area_fast = K2_AREA_FAST && P.kind == 2 && P.sw < 2 * P.dw && P.sh < 2 * P.dh && q420;
+  // linear fast path: kind 3 with the SSE2 vertical body on every element
+  // (every RRC crop that is upscaled along some axis at out_w 224)
+  if (!(((P.kind == 3 && P.vec_end == 3 * out_w) || area_fast) && (out_w & 1) == 0 && out_w <= 2 * K2_COLS && pow2)) {
+    o->fmt = K2B_GENERAL;  // (nothing else is read)
+    return;
+  }
+  const int oy0 = band * BAND, oy1 = min(out_h, oy0 + BAND);
+  int r0, r1;
+  band_rows(P, oy0, oy1, &r0, &r1);
+  const int nrows = r1 - r0 + 1;
+  o->r0 = r0;
+  o->nrows = nrows;
+  const int ri = g.ri(), rj = g.rj(), rw = g.rw();
+  o->ri = ri;
+  o->rj = rj;
+  o->rw = rw;
+  o->sw = P.sw;
+  o->sh = P.sh;
+  o->scale_x = P.scale_x;
+  o->scale_y = P.scale_y;
+  // LDS: [LUT][row taps][component tiles, dword rows][crop rows]
+  int need = lut_b + (area_fast ? (int)sizeof(AreaTaps) : (int)sizeof(LinTap)) * BAND;
+  uint32_t fmt = area_fast ? K2B_AREA : K2B_LINEAR;
+  fmt |= (q420 ? K2B_Q420 : 0u) | (taps ? K2B_TAPS : 0u) | ((uint32_t)ncomp << K2B_NCOMP_SH) | (g.color_rgb() ? K2B_RGB : 0u);
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (c >= ncomp) {
+      o->pbase[c] = 0;
+      o->tyx[c] = o->trp[c] = o->tos[c] = o->cwh[c] = 0;
+      continue;
+    }
+    const int he = g.he(c), ve = g.ve(c), hsh = he >> 1, vsh = ve >> 1;  // 1 / 2 / 4 -> 0 / 1 / 2
+    const int cw = g.cw(c), ch = g.ch(c), stride = g.stride(c);
+    fmt |= ((uint32_t)hsh | ((uint32_t)vsh << 2)) << (K2B_EXP_SH + 4 * c);
+    int y0 = ((ri + r0) >> vsh) - (ve == 2 ? 1 : 0), y1 = ((ri + r1) >> vsh) + (ve == 2 ? 1 : 0);
+    int x0 = (rj >> hsh) - (he == 2 ? 1 : 0), x1 = ((rj + rw - 1) >> hsh) + (he == 2 ? 1 : 0);
+    y0 = max(y0, 0);
+    x0 = max(x0, 0);
+    y1 = min(y1, ch - 1);
+    x1 = min(x1, cw - 1);
+    const int tx0 = x0 & ~3;  // whole dwords of the plane row (rows are 8-byte aligned)
+    const int trows = y1 - y0 + 1, tpitch = ((x1 + 4) & ~3) - tx0;
+    o->pbase[c] = g.poff(c) + (uint64_t)y0 * stride + tx0;
+    o->tyx[c] = (uint32_t)y0 | ((uint32_t)tx0 << 16);
+    o->trp[c] = ((uint32_t)trows & 0xffffu) | ((uint32_t)tpitch << 16);
+    o->tos[c] = ((uint32_t)need & 0xffffu) | ((uint32_t)(stride >> 3) << 16);
+    o->cwh[c] = (uint32_t)cw | ((uint32_t)ch << 16);
+    need += trows * tpitch;
+  }
+  const int rgb_off = need;
+  // area: RGB rows from luma column Xb = 2 * (rj >> 1) (the colour pass's
+  // first quad column), 12 bytes per chroma column pair, 4-byte aligned;
+  // + 16 bytes for the walk's aligned reads past the last row's end
+  const int pitch3 = 12 * (((((rj + rw - 1) >> 1) - (rj >> 1)) + 2) >> 1);
+  need += area_fast ? nrows * pitch3 + 16 : nrows * rw * 4 + 4;  // linear: + a dummy word for off-crop pixels
+  o->rgbp = ((uint32_t)rgb_off & 0xffffu) | ((uint32_t)pitch3 << 16);
+  o->need = need;
+  // (a fast band's packed halves fit, see K2BandRec; a band that turns out
+  // general here has low halves cut to 16 bits and high halves that may have
+  // lost bits: K2 reads none of them under K2B_GENERAL)
+  o->fmt = need <= K2_LDS ? fmt : (uint32_t)K2B_GENERAL;
+}
+
+// The geometry k2_write_band_rec reads, from an image record.
+struct InfoGeom {
+  const ImgInfo &I;
+  FFCV_DEV int ncomp() const { return I.ncomp; }
+  FFCV_DEV int color_rgb() const { return I.color_rgb; }
+  FFCV_DEV int he(int c) const { return I.he[c]; }
+  FFCV_DEV int ve(int c) const { return I.ve[c]; }
+  FFCV_DEV int cw(int c) const { return I.cw[c]; }
+  FFCV_DEV int ch(int c) const { return I.ch[c]; }
+  FFCV_DEV int stride(int c) const { return I.stride[c]; }
+  FFCV_DEV uint64_t poff(int c) const { return I.poff[c]; }
+  FFCV_DEV int ri() const { return I.ri; }
+  FFCV_DEV int rj() const { return I.rj; }
+  FFCV_DEV int rw() const { return I.rw; }
+};
 
 // Huffman decode tables built from one image's DHT segments.  K1 runs JW
 // images per workgroup; images whose tables (and table slots) are byte-
@@ -926,6 +1068,9 @@ struct JpegArgs {
   // (the sample id comes from ids[k]).
   uint32_t *eidx;
   uint64_t eidx_n;
+  // RRC: brec_bands = ceil(out_h / BAND) K2 band records per image, written by K1b
+  K2BandRec *brec;
+  int brec_bands;
 };
 
 // Diagnostic stamps: lane 0 records wall_clock64 at phase boundaries into
@@ -2172,6 +2317,11 @@ __global__ void __launch_bounds__(K1B_T) jpeg_idct_kernel(JpegArgs a) {
   static_assert(sizeof(ImgInfo) % 4 == 0, "ImgInfo copies as dwords");
   for (int i = t; i < (int)(sizeof(ImgInfo) / 4); i += K1B_T) ((uint32_t *)&L)[i] = ((const uint32_t *)&G)[i];
   __syncthreads();
+  // K2's band records (RRC launches: brec_bands > 0), one thread per band,
+  // from the record in LDS
+  for (int b = t; b < a.brec_bands; b += K1B_T)
+    k2_write_band_rec(a.brec + ((uint64_t)k * a.brec_bands + b), InfoGeom{L}, L.plan, a.p.out_w, a.p.out_h, b,
+                      a.p.lut ? 1536 : 0, L.taps);
   int16_t *coef = (int16_t *)(a.arena + L.cf_off);
   uint8_t *planes = a.arena;
   int nbw[3];
@@ -2306,6 +2456,22 @@ struct K2Rec {
   FFCV_DEV double f64(int i) const { return __builtin_bit_cast(double, u64(i)); }
 };
 #define K2F(f) ((int)(offsetof(ImgInfo, f) / 4))
+// This band's K2BandRec (written by K1b: a previous kernel), read through the
+// scalar cache in the same round trip: 32 dwords, no lane broadcast.  The
+// phases below pick their few fields from it.
+struct K2Band {
+  const __attribute__((address_space(4))) uint32_t *p;
+  FFCV_DEV void load(const K2BandRec *rec) { p = (const __attribute__((address_space(4))) uint32_t *)rec; }
+  // A new phase reads its fields again (scalar cache hits) instead of
+  // holding them in registers from the top: the compiler must not merge
+  // these loads with the earlier phase's
+  FFCV_DEV void phase() { asm volatile("" : "+s"(p)); }
+  FFCV_DEV uint32_t u(int i) const { return p[i]; }
+  FFCV_DEV int32_t s(int i) const { return (int32_t)p[i]; }
+  FFCV_DEV uint64_t u64(int i) const { return (uint64_t)p[i] | ((uint64_t)p[i + 1] << 32); }
+  FFCV_DEV double f64(int i) const { return __builtin_bit_cast(double, u64(i)); }
+};
+#define K2BF(f) ((int)(offsetof(K2BandRec, f) / 4))
 FFCV_DEV ImgInfo k2_head(const K2Rec &R) {
   ImgInfo I;  // only the head fields are set (SROA keeps them in registers)
   I.status = R.s(K2F(status));
@@ -2357,8 +2523,17 @@ FFCV_DEV ColorGeom color_geom(const ImgInfo &I) {
   return g;
 }
 
+// The wave-uniform format fields pass through an empty asm per call: the
+// upsampling-mode tests of upsample_at are then scalar compares beside their
+// branches.  Without it the compiler hoists every (he == a && ve == b)
+// combination of three components out of the caller's per-pixel loop as
+// 64-bit masks, ~20 SGPR pairs that spilled and were reloaded per iteration.
 template <class PL>
-FFCV_DEV void pixel_rgb(const ColorGeom &I, const PL *pl, int Y, int X, int v[3]) {
+FFCV_DEV void pixel_rgb(const ColorGeom &G, const PL *pl, int Y, int X, int v[3]) {
+  ColorGeom I = G;
+  asm volatile("" : "+s"(I.ncomp), "+s"(I.color_rgb));
+#pragma unroll
+  for (int c = 0; c < 3; c++) asm volatile("" : "+s"(I.he[c]), "+s"(I.ve[c]), "+s"(I.cw[c]));
   if (I.ncomp == 1) {
     v[0] = v[1] = v[2] = pl[0].at(Y, X);
     return;
@@ -2424,9 +2599,6 @@ FFCV_DEV uint32_t lut_ld(uint32_t q, int c) { return ((const lds_u16_t *)(uintpt
 #ifndef K2_SADDR_STORE
 #define K2_SADDR_STORE 1  // 0: the linear walk's per-row 64-bit output address (A/B builds)
 #endif
-#ifndef K2_AREA_FAST
-#define K2_AREA_FAST 1  // 0: area crops take the general per-pixel path (A/B builds)
-#endif
 
 // K2's area walk: ResizeArea_Invoker (resize.cpp, INTER_AREA with both scales
 // in [1, 2)) for output columns dx0, dx0 + 1 over this thread's row group, from
@@ -2443,7 +2615,7 @@ FFCV_DEV uint32_t lut_ld(uint32_t q, int c) { return ((const lds_u16_t *)(uintpt
 // row loops and the cache test are scalar.
 typedef float k2f2 __attribute__((ext_vector_type(2)));
 template <bool FP16>
-FFCV_DEV void k2_area_walk(const Epilogue &ep, const ResizePlan &P, const AreaTaps *atab, const uint8_t *rgb,
+FFCV_DEV void k2_area_walk(const Epilogue &ep, int psw, double pscale_x, const AreaTaps *atab, const uint8_t *rgb,
                            int pitch3, int xoff3, int r0, int oy0, int oy1, int sub, int dx0, uint32_t lutb,
                            char *ob) {
   const int half = (BAND + K2T / K2_COLS - 1) / (K2T / K2_COLS);  // rows per row group
@@ -2453,7 +2625,7 @@ FFCV_DEV void k2_area_walk(const Epilogue &ep, const ResizePlan &P, const AreaTa
   uint32_t xa[2], sh[2];  // a column's first tap: aligned byte offset in the row, byte shift
   k2f2 wk[3];             // tap k's weight for (dx0, dx0 + 1)
   {
-    const AreaTaps t0 = area_taps(P.sw, P.scale_x, ep.src_x(dx0)), t1 = area_taps(P.sw, P.scale_x, ep.src_x(dx0 + 1));
+    const AreaTaps t0 = area_taps(psw, pscale_x, ep.src_x(dx0)), t1 = area_taps(psw, pscale_x, ep.src_x(dx0 + 1));
     const uint32_t o0 = (uint32_t)(xoff3 + 3 * t0.lo), o1 = (uint32_t)(xoff3 + 3 * t1.lo);
     xa[0] = o0 & ~3u;
     sh[0] = o0 & 3u;
@@ -2597,6 +2769,21 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
     if (t < band_rows_n) rt_pre = ktaps[a.p.out_w + band * BAND + t];
     if (2 * (t % K2_COLS) + 1 < a.p.out_w) ct_pre = *(const uint4 *)(ktaps + 2 * (t % K2_COLS));
   }
+  // (the band record: its selector and what the first phase, the tile
+  // staging, reads)
+  K2Band B;
+  uint32_t b_fmt = 0, b_trp[3] = {0, 0, 0}, b_tos[3] = {0, 0, 0};
+  uint64_t b_pbase[3] = {0, 0, 0};
+  if (MODE == JM_RRC) {
+    B.load(a.brec + ((uint64_t)k * a.brec_bands + band));
+    b_fmt = B.u(K2BF(fmt));
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      b_trp[c] = B.u(K2BF(trp) + c);
+      b_tos[c] = B.u(K2BF(tos) + c);
+      b_pbase[c] = B.u64(K2BF(pbase) + 2 * c);
+    }
+  }
   const int cut_y0 = a.cut ? a.cut[2 * k] : 0, cut_x0 = a.cut ? a.cut[2 * k + 1] : 0;
   const int flip0 = a.flips ? a.flips[k] : 0;
   if (k == 0 && band == 0 && t == 0) {  // K1 is done: close its arena (see arena_before_k1)
@@ -2606,8 +2793,7 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
       a.arena_top[0] = 0;
     }
   }
-  const ImgInfo I = k2_head(R);
-  const int status = I.status;
+  const int status = R.s(K2F(status));
   if (status == -1) return;  // raw sample (handled by the raw kernel)
   const int out_h = MODE == JM_FULL ? (int)a.samples[k].height : a.p.out_h;
   const int out_w = MODE == JM_FULL ? (int)a.samples[k].width : a.p.out_w;
@@ -2622,13 +2808,12 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
     }
     return;
   }
-  const uint8_t *planes = a.arena;
-  const ColorGeom G = color_geom(I);
-  const int ncomp = G.ncomp;
-  GPlane gp[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) gp[c] = GPlane{planes + I.poff[c], I.stride[c]};
   if (MODE == JM_FULL) {
+    const ImgInfo I = k2_head(R);
+    const ColorGeom G = color_geom(I);
+    GPlane gp[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) gp[c] = GPlane{a.arena + I.poff[c], I.stride[c]};
     uint8_t *o = (uint8_t *)ob;
     for (int i = t; i < (oy1 - oy0) * out_w; i += K2T) {
       int y = oy0 + i / out_w, x = i % out_w;
@@ -2646,13 +2831,6 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
     for (int u = 0; u < LU; u++)
       if (u * K2T + t < 768) s_lut[u * K2T + t] = lv[u];
   }
-  const int ri = I.ri, rj = I.rj, rh = I.rh, rw = I.rw;
-  const ResizePlan P = MODE == JM_RRC ? I.plan : make_plan(rw, rh, out_w, out_h);  // RRC: K1's plan
-  const uint2 *taps = I.taps ? ktaps : nullptr;
-  int r0, r1;
-  band_rows(P, oy0, oy1, &r0, &r1);
-  const int nrows = r1 - r0 + 1;
-  const int step = rw * 3;
   // Epilogue parameters (flip, cutout) of this image
   Epilogue ep;
   ep.out_h = out_h;
@@ -2666,71 +2844,38 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
   ep.fill[1] = a.p.cutout_fill[1];
   ep.fill[2] = a.p.cutout_fill[2];
 
-  // ---- linear fast path (kind 3 with the SSE2 vertical body on every
-  // element: every RRC crop that is upscaled along some axis at out_w 224).
+  // ---- fast paths, selected per band by K1b (k2_write_band_rec).
+  // Linear (kind 3 with the SSE2 vertical body on every element: every RRC
+  // crop that is upscaled along some axis at out_w 224).
   // LDS: [LUT][row taps][component tiles, dword rows][crop rows as RGBx
   // words].  Each thread owns one output column pair and walks its half of
   // the band's rows, keeping the two source rows' horizontal sums in
   // registers (resize.cpp HResizeLinear -> VResizeLinearVec_32s8u).
-  // expansion factors 1 / 2 / 4 (every common subsampling): the tile bounds
-  // below divide by shifts (a runtime x / ve compiles to a ~25-instruction
-  // VALU sequence, twelve per workgroup); 3 takes the general path
-  auto p2 = [](int x) { return x == 1 || x == 2 || x == 4; };
-  const bool pow2 = p2(G.he[0]) && p2(G.ve[0]) && p2(G.he[1]) && p2(G.ve[1]) && p2(G.he[2]) && p2(G.ve[2]);
-  // area fast path (round 6): INTER_AREA crops with both scales in [1, 2)
-  // (every RRC crop larger than the output on both axes, up to 2x) of 4:2:0
-  // images: the same tiles and colour pass, the crop rows kept as packed RGB
-  // (3 bytes per pixel: 4-byte words would not fit a band's ~20 rows of up to
-  // 256 px), then a column-pair walk with one cached row of horizontal sums
-  // (as rrc_raw_kernel's area walk).  These bands took the general per-pixel
+  // Area (round 6): INTER_AREA crops with both scales in [1, 2) (every RRC
+  // crop larger than the output on both axes, up to 2x) of 4:2:0 images: the
+  // same tiles and colour pass, the crop rows kept as packed RGB (3 bytes per
+  // pixel: 4-byte words would not fit a band's ~20 rows of up to 256 px), then
+  // a column-pair walk with one cached row of horizontal sums (as
+  // rrc_raw_kernel's area walk).  These bands took the general per-pixel
   // path before, ~3x the time of a linear band (r5z2_c3_k2_by_crop_perband.log).
-  // (scale_x = 1 / (dw / sw) < 2 exactly when sw < 2 dw: integer tests keep
-  // the f64 scales out of this condition, which cost 11 VGPRs)
-  const bool area_fast = K2_AREA_FAST && P.kind == 2 && P.sw < 2 * P.dw && P.sh < 2 * P.dh && ncomp == 3 &&
-                         !G.color_rgb && G.he[0] == 1 && G.ve[0] == 1 && G.he[1] == 2 && G.ve[1] == 2 &&
-                         G.he[2] == 2 && G.ve[2] == 2 && G.cw[1] > 2 && G.cw[2] > 2;
-  if (((P.kind == 3 && P.vec_end == 3 * out_w) || area_fast) && (out_w & 1) == 0 && out_w <= 2 * K2_COLS && pow2) {
+  if (MODE == JM_RRC && (b_fmt & 3u) != K2B_GENERAL) {
+    const uint32_t fmt = b_fmt;
+    const bool area_fast = (fmt & 3u) == K2B_AREA;
     const int lut_b = FP16 ? 1536 : 0;
     LinTap *rtab = (LinTap *)(lds + lut_b);
     AreaTaps *atab = (AreaTaps *)(lds + lut_b);
-    int ty0[3], tx0[3], trows[3], tpitch[3], toff[3];
-    int need = lut_b + (area_fast ? (int)sizeof(AreaTaps) : (int)sizeof(LinTap)) * BAND;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      if (c >= ncomp) {
-        ty0[c] = tx0[c] = trows[c] = tpitch[c] = toff[c] = 0;
-        continue;
-      }
-      const int he = G.he[c], ve = G.ve[c], hsh = he >> 1, vsh = ve >> 1;  // 1 / 2 / 4 -> 0 / 1 / 2
-      int y0 = ((ri + r0) >> vsh) - (ve == 2 ? 1 : 0), y1 = ((ri + r1) >> vsh) + (ve == 2 ? 1 : 0);
-      int x0 = (rj >> hsh) - (he == 2 ? 1 : 0), x1 = ((rj + rw - 1) >> hsh) + (he == 2 ? 1 : 0);
-      y0 = max(y0, 0);
-      x0 = max(x0, 0);
-      y1 = min(y1, G.ch[c] - 1);
-      x1 = min(x1, G.cw[c] - 1);
-      ty0[c] = y0;
-      tx0[c] = x0 & ~3;  // whole dwords of the plane row (rows are 8-byte aligned)
-      trows[c] = y1 - y0 + 1;
-      tpitch[c] = ((x1 + 4) & ~3) - tx0[c];
-      toff[c] = need;
-      need += trows[c] * tpitch[c];
-    }
-    const int rgb_off = need;
-    // area: RGB rows from luma column Xb = 2 * (rj >> 1) (the colour pass's
-    // first quad column), 12 bytes per chroma column pair, 4-byte aligned;
-    // + 16 bytes for the walk's aligned reads past the last row's end
-    const int pitch3 = 12 * (((((rj + rw - 1) >> 1) - (rj >> 1)) + 2) >> 1);
-    need += area_fast ? nrows * pitch3 + 16 : nrows * rw * 4 + 4;  // linear: + a dummy word for off-crop pixels
-    if (need <= K2_LDS) {
-      K2_STOP_AT(1, a.out_stride != 77);  // diagnostics: the band's set-up (record, LUT, taps, tile bounds)
-      uint32_t *rgbx = (uint32_t *)(lds + rgb_off);
+    const uint2 *taps = (fmt & K2B_TAPS) ? ktaps : nullptr;
+    {
+      K2_STOP_AT(1, a.out_stride != 77);  // diagnostics: the band's set-up (record, LUT, taps)
+      // ---- phase 1: row taps and tile staging
       if (!area_fast && t < oy1 - oy0) {  // weights stored as the walk's multiplier operands, c << 8 (see hrow)
-        LinTap lt = taps ? tap_unpack(rt_pre) : lin_tap(P.scale_y, P.inv_y, P.sh, oy0 + t);
+        // (no table: out_w + out_h > K2_TAPS; the f64 scales come from the image record)
+        LinTap lt = taps ? tap_unpack(rt_pre)
+                         : lin_tap(R.f64(K2F(plan.scale_y)), R.f64(K2F(plan.inv_y)), B.s(K2BF(sh)), oy0 + t);
         lt.c0 = (lt.c0 & 0xfff) << 8;
         lt.c1 = (lt.c1 & 0xfff) << 8;
         rtab[t] = lt;
       }
-      TPlane tp[3];
       // tile staging: the first SU dwords per thread of every component are
       // loaded before any LDS write (one memory round trip, not one per
       // dword); row = i / wpr by a float reciprocal: exact while the +0.5
@@ -2746,10 +2891,11 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
       typedef const __attribute__((address_space(1))) uint8_t gu8_t;
 #pragma unroll
       for (int c = 0; c < 3; c++) {
-        const int wpr = max(tpitch[c] >> 2, 1), n = trows[c] * (tpitch[c] >> 2);
+        const int trows = (int)(b_trp[c] & 0xffffu), tpitch = (int)(b_trp[c] >> 16);
+        const int wpr = max(tpitch >> 2, 1), n = trows * (tpitch >> 2);
         const float rwp = __builtin_amdgcn_rcpf((float)wpr);  // (1 ulp: far inside the +0.5 margin)
-        gu8_t *src = (gu8_t *)(uintptr_t)(gp[c].p + (uint64_t)ty0[c] * gp[c].stride + tx0[c]);
-        const uint32_t st = (uint32_t)gp[c].stride;
+        gu8_t *src = (gu8_t *)(uintptr_t)(a.arena + b_pbase[c]);
+        const uint32_t st = (b_tos[c] >> 16) << 3;
 #pragma unroll
         for (int u = 0; u < SU; u++) {
           const int i = u * K2T + t;
@@ -2759,27 +2905,39 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
       }
 #pragma unroll
       for (int c = 0; c < 3; c++) {
-        uint32_t *tl = (uint32_t *)(lds + toff[c]);
-        const int wpr = max(tpitch[c] >> 2, 1), n = trows[c] * (tpitch[c] >> 2);
+        const int trows = (int)(b_trp[c] & 0xffffu), tpitch = (int)(b_trp[c] >> 16);
+        uint32_t *tl = (uint32_t *)(lds + (b_tos[c] & 0xffffu));
+        const int wpr = max(tpitch >> 2, 1), n = trows * (tpitch >> 2);
 #pragma unroll
         for (int u = 0; u < SU; u++)
           if (u * K2T + t < n) tl[u * K2T + t] = sv[c][u];
-        const uint8_t *src = gp[c].p + (uint64_t)ty0[c] * gp[c].stride + tx0[c];
+        const uint8_t *src = a.arena + b_pbase[c];
+        const uint32_t st = (b_tos[c] >> 16) << 3;
         const float rwp = __builtin_amdgcn_rcpf((float)wpr);
         for (int i = SU * K2T + t; i < n; i += K2T) {  // big tiles
           const int rr = (int)(((float)i + 0.5f) * rwp), q = i - __mul24(rr, wpr);
-          tl[i] = *(const uint32_t *)(src + (uint64_t)rr * gp[c].stride + 4 * q);
+          tl[i] = *(const uint32_t *)(src + (uint64_t)rr * st + 4 * q);
         }
-        tp[c] = TPlane{(const uint8_t *)tl, ty0[c], tx0[c], tpitch[c]};
       }
       // (after the tiles: its f64 arithmetic would raise the register peak
       // while the tile loads are in flight)
-      if (area_fast && t < oy1 - oy0) atab[t] = area_taps(P.sh, P.scale_y, oy0 + t);
+      if (area_fast && t < oy1 - oy0) atab[t] = area_taps(B.s(K2BF(sh)), B.f64(K2BF(scale_y)), oy0 + t);
       __syncthreads();
       K2_STOP_AT(2, a.out_stride != 77);  // diagnostics: + the plane tiles
-      const int Y0 = ri + r0, Y1 = ri + r1, X0 = rj, X1 = rj + rw - 1;
-      if (ncomp == 3 && !G.color_rgb && G.he[0] == 1 && G.ve[0] == 1 && G.he[1] == 2 && G.ve[1] == 2 &&
-          G.he[2] == 2 && G.ve[2] == 2 && G.cw[1] > 2 && G.cw[2] > 2) {  // (every area_fast band)
+      // ---- phase 2: the colour pass, on its own fields of the record
+      B.phase();
+      TPlane tp[3];
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const uint32_t tyx = B.u(K2BF(tyx) + c);
+        tp[c] = TPlane{lds + (B.u(K2BF(tos) + c) & 0xffffu), (int)(tyx & 0xffffu), (int)(tyx >> 16),
+                       (int)(B.u(K2BF(trp) + c) >> 16)};
+      }
+      const int r0c = B.s(K2BF(r0)), nrows = B.s(K2BF(nrows)), rw = B.s(K2BF(rw));
+      const int Y0 = B.s(K2BF(ri)) + r0c, Y1 = Y0 + nrows - 1, X0 = B.s(K2BF(rj)), X1 = X0 + rw - 1;
+      uint32_t *rgbx = (uint32_t *)(lds + (B.u(K2BF(rgbp)) & 0xffffu));
+      const int pitch3 = (int)(B.u(K2BF(rgbp)) >> 16);
+      if (fmt & K2B_Q420) {  // (every area_fast band)
         // 4:2:0 (jdsample.c h2v2_fancy_upsample, as upsample_quad_h2v2): each
         // thread owns a pair of adjacent chroma columns (C, C + 1) and walks
         // every ng-th chroma row of the band.  Column clamps, edge terms and
@@ -2800,7 +2958,7 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
           const int C = C0 + 2 * pr;
           // plane columns of the two quads' neighbourhoods (clamped like
           // upsample_quad_h2v2; the fourth is unused without a second quad)
-          const int cw = G.cw[1], ch = G.ch[1];
+          const int cw = (int)(B.u(K2BF(cwh) + 1) & 0xffffu), ch = (int)(B.u(K2BF(cwh) + 1) >> 16);
           const int xm = max(C - 1, 0) - tp[1].c0, x0 = C - tp[1].c0;
           const int x1 = min(C + 1, cw - 1) - tp[1].c0, x2 = min(C + 2, min(C1 + 1, cw - 1)) - tp[1].c0;
           // luma columns 2C .. 2C + 3: inside the crop?  (reads clamped into it)
@@ -2875,6 +3033,16 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
           }
         }
       } else {
+        ColorGeom G;  // (the record's packed format)
+        G.ncomp = (int)((fmt >> K2B_NCOMP_SH) & 3u);
+        G.color_rgb = (fmt & K2B_RGB) != 0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          G.he[c] = 1 << ((fmt >> (K2B_EXP_SH + 4 * c)) & 3u);
+          G.ve[c] = 1 << ((fmt >> (K2B_EXP_SH + 4 * c + 2)) & 3u);
+          G.cw[c] = (int)(B.u(K2BF(cwh) + c) & 0xffffu);
+          G.ch[c] = (int)(B.u(K2BF(cwh) + c) >> 16);
+        }
         for (int i = t; i < nrows * rw; i += K2T) {
           const int yy = i / rw, x = i - yy * rw;
           int v[3];
@@ -2887,19 +3055,27 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
       const int tx = t % K2_COLS, sub = t / K2_COLS;
       if (tx >= out_w / 2) return;
       const int dx0 = 2 * tx;
+      // ---- phase 3: the walk, on its own fields of the record
+      B.phase();
+      const int r0 = B.s(K2BF(r0)), psh = B.s(K2BF(sh));
+      const uint32_t *wrgb = (const uint32_t *)(lds + (B.u(K2BF(rgbp)) & 0xffffu));
       if (area_fast) {
-        k2_area_walk<FP16>(ep, P, atab, (const uint8_t *)rgbx, pitch3, 3 * (rj - 2 * (rj >> 1)), r0, oy0, oy1, sub,
-                           dx0, lut_base(s_lut), ob);
+        const int rj = B.s(K2BF(rj));
+        k2_area_walk<FP16>(ep, B.s(K2BF(sw)), B.f64(K2BF(scale_x)), atab, (const uint8_t *)wrgb,
+                           (int)(B.u(K2BF(rgbp)) >> 16), 3 * (rj - 2 * (rj >> 1)), r0, oy0, oy1, sub, dx0,
+                           lut_base(s_lut), ob);
         return;
       }
+      const int wrw = B.s(K2BF(rw));
       LinTap l0, l1;
       if (taps) {  // K1's table (flip applied): both columns in one 16-byte load (at the top)
         const uint4 q = ct_pre;
         l0 = tap_unpack(make_uint2(q.x, q.y));
         l1 = tap_unpack(make_uint2(q.z, q.w));
       } else {
-        l0 = lin_tap(P.scale_x, P.inv_x, P.sw, ep.src_x(dx0));
-        l1 = lin_tap(P.scale_x, P.inv_x, P.sw, ep.src_x(dx0 + 1));
+        const double sx = R.f64(K2F(plan.scale_x)), ix = R.f64(K2F(plan.inv_x));
+        l0 = lin_tap(sx, ix, B.s(K2BF(sw)), ep.src_x(dx0));
+        l1 = lin_tap(sx, ix, B.s(K2BF(sw)), ep.src_x(dx0 + 1));
       }
       // a border tap (src[s] * 2048) as the same two-tap form with weights
       // (2048, 0) on (s, s + 1): branch-free, identical sums
@@ -2922,7 +3098,7 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
       const uint32_t w0 = ((uint32_t)a0w << 4) | ((uint32_t)b0w << 20), w1 = ((uint32_t)a1w << 4) | ((uint32_t)b1w << 20);
       const uint32_t so0 = 4u * (uint32_t)l0.s, so1 = 4u * (uint32_t)l1.s;  // byte offsets in a row
       auto hrow = [&](int r, uint32_t H[6]) {
-        const uint32_t *row = rgbx + __mul24(r - r0, rw);
+        const uint32_t *row = wrgb + __mul24(r - r0, wrw);
         // words s and s + 1 as one ds_read2 per column (a border tap's second
         // word has weight 0: at the crop's right edge it is the next row's
         // first word or, in the last row, the dummy word)
@@ -2957,7 +3133,7 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
       uint32_t HA[6], HB[6];
       for (int dy = ya; dy < yb; dy++) {
         const LinTap ly = rtab[dy - oy0];
-        const int ra = min(max(ly.s, 0), P.sh - 1), rb = min(max(ly.s + 1, 0), P.sh - 1);
+        const int ra = min(max(ly.s, 0), psh - 1), rb = min(max(ly.s + 1, 0), psh - 1);
         if (ra != ca) {
           if (ra == cb) {
 #pragma unroll
@@ -3028,6 +3204,20 @@ FFCV_DEV void k2_band(const JpegArgs &a, const int k, const int band, uint8_t *l
       return;
     }
   }
+  // ---- general path: the image record's head (as every band before the
+  // band records), its own set-up
+  const ImgInfo I = k2_head(R);
+  const ColorGeom G = color_geom(I);
+  const int ncomp = G.ncomp;
+  GPlane gp[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) gp[c] = GPlane{a.arena + I.poff[c], I.stride[c]};
+  const int ri = I.ri, rj = I.rj, rw = I.rw;
+  const ResizePlan P = I.plan;  // K1's plan
+  int r0, r1;
+  band_rows(P, oy0, oy1, &r0, &r1);
+  const int nrows = r1 - r0 + 1;
+  const int step = rw * 3;
   // diagnostics (K1's stamp buffer, slot 11): bands of this image that take
   // the general path below
   if (a.dbg && t == 0) atomicAdd((unsigned long long *)(a.dbg + (uint64_t)k * 16 + 11), 1ull);
@@ -3247,6 +3437,21 @@ __global__ void __launch_bounds__(K2T) __attribute__((amdgpu_waves_per_eu(K2_WPE
   k2_band<MODE, FP16>(a, (int)blockIdx.y, (int)blockIdx.x, lds);
 }
 
+// Diagnostics only (ffcv_jpeg_set_diag): a launch that runs K2 without K1b
+// re-runs it on the previous launch's scratch, whose band records may be for
+// another output size; this kernel rewrites them from the image records, one
+// thread per (image, band), so K2 never reads records its own launch did not
+// write.  The product path has no such launch: K1b writes them.
+__global__ void __launch_bounds__(256) k2_rec_kernel(JpegArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int k = i / a.brec_bands, b = i - k * a.brec_bands;
+  if (k >= a.batch) return;
+  const ImgInfo &I = a.info[k];
+  if (I.status != FFCV_SAMPLE_OK) return;
+  // (the image record's plan and tap table: what such a launch's K2 used before)
+  k2_write_band_rec(a.brec + i, InfoGeom{I}, I.plan, a.p.out_w, a.p.out_h, b, a.p.lut ? 1536 : 0, I.taps);
+}
+
 // ---------------------------------------------------------------- ctx -----
 struct ffcv_jpeg_ctx {
   uint64_t *dbg;
@@ -3260,6 +3465,8 @@ struct ffcv_jpeg_ctx {
   bool arena_zero;  // [0] is 0 at the stream's tail: the last launch ran K2, which zeroes it
   ImgInfo *info;
   uint2 *taps;
+  K2BandRec *brec;  // K2's band records: max_batch x brec_cap (launch_rrc grows it for taller outputs)
+  int brec_cap;
   uint8_t *gtab;
   uint32_t *k1_order;  // max_batch slots (k1_order_kernel); used when k1_sorted
   bool k1_sorted;
@@ -3287,6 +3494,7 @@ static void free_ctx(ffcv_jpeg_ctx *c) {
   (void)hipFree(c->arena_top);
   (void)hipFree(c->info);
   (void)hipFree(c->taps);
+  (void)hipFree(c->brec);
   (void)hipFree(c->gtab);
   (void)hipFree(c->k1_order);
   delete c;
@@ -3329,6 +3537,7 @@ int ffcv_jpeg_create_arena(ffcv_jpeg_ctx **out, int max_batch, uint32_t max_heig
       (e = hipMemset(c->arena_top, 0, 2 * sizeof(unsigned long long))) != hipSuccess ||
       (e = hipMalloc(&c->info, sizeof(ImgInfo) * max_batch)) != hipSuccess ||
       (e = hipMalloc(&c->taps, sizeof(uint2) * K2_TAPS * max_batch)) != hipSuccess ||
+      (e = hipMalloc(&c->brec, sizeof(K2BandRec) * K2_REC_BANDS * max_batch)) != hipSuccess ||
       (e = hipMalloc(&c->gtab, c->gtab_slot * max_batch)) != hipSuccess ||
       (e = hipMalloc(&c->k1_order, sizeof(uint32_t) * max_batch)) != hipSuccess ||
       // the memset above runs on the null stream, which the caller's
@@ -3340,6 +3549,7 @@ int ffcv_jpeg_create_arena(ffcv_jpeg_ctx **out, int max_batch, uint32_t max_heig
     free_ctx(c);
     return rc;
   }
+  c->brec_cap = K2_REC_BANDS;
   c->arena_zero = false;  // the first launch also zeroes the counter, on its own stream
   *out = c;
   return FFCV_OK;
@@ -3546,6 +3756,24 @@ static int launch_rrc(ffcv_jpeg_ctx *c, JpegArgs &a, hipStream_t s, const ffcv_r
   uint64_t dense = (uint64_t)p->out_h * p->out_w * 3 * (fp16 ? 2 : 1);
   a.out_stride = p->out_stride ? p->out_stride : dense;
   const int only = a.diag_only;
+  // K2's band records: ceil(out_h / BAND) per image.  The buffer holds
+  // K2_REC_BANDS per image (out_h <= 256); a taller output grows it once, a
+  // cold path that synchronises the device (include/ffcv_hip.h says so) and
+  // fails under stream capture, where hipMalloc is refused, before anything
+  // is freed.  Records do not outlive their launch (K1b rewrites them), so
+  // nothing is copied over; earlier launches on any stream may still read
+  // the old buffer, and hipFree returns only after they have finished.  This
+  // launch's kernels are enqueued after the swap and only see the new one.
+  const int nb = (p->out_h + BAND - 1) / BAND;
+  if (nb > c->brec_cap) {
+    K2BandRec *nbuf = nullptr;
+    FFCV_HIP_CHECK(hipMalloc(&nbuf, sizeof(K2BandRec) * (size_t)nb * c->max_batch));
+    (void)hipFree(c->brec);
+    c->brec = nbuf;
+    c->brec_cap = nb;
+  }
+  a.brec = c->brec;
+  a.brec_bands = nb;
   if (only & 1) {
     if (int rc = arena_before_k1(c, a, s)) return rc;
   }
@@ -3568,8 +3796,12 @@ static int launch_rrc(ffcv_jpeg_ctx *c, JpegArgs &a, hipStream_t s, const ffcv_r
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3(batch), dim3(K1B_T), 0, s, a);
     FFCV_LAUNCH_CHECK("jpeg_idct_kernel");
   }
+  if ((only & 4) && !(only & 2)) {  // diagnostics: K2 without K1b (see k2_rec_kernel)
+    hipLaunchKernelGGL(k2_rec_kernel, dim3((unsigned)(((uint64_t)batch * nb + 255) / 256)), dim3(256), 0, s, a);
+    FFCV_LAUNCH_CHECK("k2_rec_kernel");
+  }
   if (ev) FFCV_HIP_CHECK(hipEventRecord(ev[2], s));
-  dim3 g2((p->out_h + BAND - 1) / BAND, batch);
+  dim3 g2(nb, batch);
   if (!(only & 4)) {
   } else if (fp16)
     hipLaunchKernelGGL((jpeg_color_resize_kernel<JM_RRC, true>), g2, dim3(K2T), K2_LDS, s, a);

@@ -287,7 +287,13 @@ int ffcv_jpeg_arena_used(ffcv_jpeg_ctx *ctx, void *stream, uint64_t *used,
 /* rgb_image.py:185-210 jpg branch fused end to end: decode only the MCUs the
  * crop needs -> crop -> INTER_AREA -> cutout -> LUT.  Samples with mode !=
  * jpg are skipped (call ffcv_rrc_raw_batch for them).  status: device
- * int32[B] (FFCV_SAMPLE_*), required. */
+ * int32[B] (FFCV_SAMPLE_*), required.
+ * A context is created with per-band scratch for outputs of up to 256 rows.
+ * The first launch on it (this call or ffcv_jpeg_rrc_fused) whose out_h is
+ * larger re-allocates that scratch for the new height: that one call
+ * synchronises the whole device (hipMalloc + hipFree) and must not be made
+ * under stream capture; it fails with the HIP error there.  Launch once at
+ * the largest out_h before capturing or before timing. */
 int ffcv_jpeg_rrc_batch(ffcv_jpeg_ctx *ctx, void *stream, const uint8_t *base,
                         const ffcv_sample *samples, int batch,
                         const int32_t *crops, const int32_t *cutout_yx,

@@ -1,0 +1,68 @@
+"""Register budgets of the JPEG kernels, from the compiler's own resource
+remarks of a device-only compile with the library's flags (no GPU needed).
+
+K2 (`jpeg_color_resize_kernel<0, *>`) must stay at 64 VGPRs or fewer with no
+scratch (what fits beside four K1 workgroups); K1 and K1b keep
+their VGPR counts and occupancy, K1b no scratch, K1 the 32 bytes per lane of
+its out-of-line draw helpers.  K2's SGPR spills: 196 (fp16) and 198 (u8) slots
+before the per-band record, 55 and 55 with it.  The goal of 0 is not reached:
+6 / 7 slots belong to the fast paths (none read or written inside a loop) and
+the rest to the general per-pixel path, which keeps the image record's head
+(DESIGN.md s3 lists them).  Each instantiation is pinned to its own count, so
+that any new spill fails here; a change that removes some lowers the bound.
+"""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'ffcv_amd', 'csrc')
+
+K1 = '_Z19jpeg_entropy_kernelILi0EEv8JpegArgs'
+K1B = '_Z16jpeg_idct_kernel8JpegArgs'
+K2_FP16 = '_Z24jpeg_color_resize_kernelILi0ELb1EEv8JpegArgs'
+K2_U8 = '_Z24jpeg_color_resize_kernelILi0ELb0EEv8JpegArgs'
+
+
+@pytest.fixture(scope='module')
+def usage():
+    from ffcv_amd import _build
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    if not os.path.exists(hipcc):
+        pytest.skip('hipcc not available')
+    flags = [f for f in _build.FLAGS if f != '-shared']
+    cmd = [hipcc] + flags + ['--cuda-device-only', '-c', '-Rpass-analysis=kernel-resource-usage', '-o', os.devnull,
+                             'ffcv_jpeg.hip']
+    err = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stderr
+    out, cur = {}, None
+    for line in err.splitlines():
+        m = re.search(r'remark:\s+(.*?) \[-Rpass-analysis', line)
+        if not m:
+            continue
+        key, _, val = m.group(1).strip().partition(':')
+        if key == 'Function Name':
+            cur = out.setdefault(val.strip(), {})
+        elif cur is not None and val.strip().lstrip('-').isdigit():
+            cur[key.strip()] = int(val)
+    return out
+
+
+@pytest.mark.parametrize('kernel,spills', [(K2_FP16, 55), (K2_U8, 55)])
+def test_k2_budget(usage, kernel, spills):
+    u = usage[kernel]
+    print(kernel, u)
+    assert u['VGPRs'] <= 64
+    assert u['ScratchSize [bytes/lane]'] == 0
+    assert u['VGPRs Spill'] == 0
+    assert u['Occupancy [waves/SIMD]'] >= 7
+    assert u['SGPRs Spill'] <= spills
+
+
+def test_k1_and_k1b_keep_their_budgets(usage):
+    k1, k1b = usage[K1], usage[K1B]
+    print(k1, k1b)
+    assert k1['VGPRs'] <= 105 and k1['Occupancy [waves/SIMD]'] >= 4 and k1['ScratchSize [bytes/lane]'] <= 32
+    assert k1b['VGPRs'] <= 105 and k1b['Occupancy [waves/SIMD]'] >= 4 and k1b['ScratchSize [bytes/lane]'] == 0
+    assert k1b['SGPRs Spill'] == 0 and k1b['VGPRs Spill'] == 0 and k1['VGPRs Spill'] == 0
