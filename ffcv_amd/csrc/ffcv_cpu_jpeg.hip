@@ -1089,4 +1089,29 @@ int ffcv_jpeg_scan_stats(const uint8_t *const *data, const uint64_t *sizes, int 
   return rc;
 }
 
+// Test helper: the coefficients of every coded block of one JPEG, in scan
+// (MCU) order, 64 per block in natural order with the absolute DC -- the
+// layout of ffcv_jpeg_coefficients_batch's rows, from the CPU decoder's
+// Huffman loop.  Blocks past max_blocks are counted, not written.  Not part of
+// the public header: libffcv.cpu_jpeg_coefficients binds it for the tests.
+int ffcv_cpu_jpeg_coefficients(const uint8_t *data, uint64_t size, int16_t *coefs, uint64_t max_blocks,
+                               uint64_t *nblocks) {
+  if (!data || !coefs || !nblocks) {
+    ffcv::set_error("ffcv_cpu_jpeg_coefficients: invalid arguments");
+    return FFCV_EINVAL;
+  }
+  Dec d;
+  if (const char *err = parse(data, size, d)) {
+    ffcv::set_error("ffcv_cpu_jpeg_coefficients: %s", err);
+    return -1;
+  }
+  uint64_t k = 0;
+  decode_scan(data, d, [&](int, int, int, const int16_t *blk) {
+    if (k < max_blocks) std::memcpy(coefs + k * 64, blk, 64 * sizeof(int16_t));
+    k++;
+  });
+  *nblocks = k;
+  return FFCV_OK;
+}
+
 }  // extern "C"

@@ -107,6 +107,17 @@ static_assert(FB_AC <= 11, "FB_AC > 11 is not supported: a 12-bit build failed t
 #define ACS_Z 24        // zigzag positions of a block the write pass stages in LDS
 #endif
 #define ACS_BYTES (ACS_Z * 2)
+// AC steps per chunk of the write pass (write_range): the per-block work runs
+// once per chunk.  2, 3 and 4 were measured.
+#ifndef K1_WCHUNK
+#define K1_WCHUNK 4
+#endif
+static_assert(K1_WCHUNK >= 1 && K1_WCHUNK <= 8, "K1_WCHUNK outside 1..8 is not supported: past 8 a flat block idles through most of its chunk (tools/sync_sim.c chunks)");
+#ifdef K1_WCHUNK_ROLLED
+#define K1_WCHUNK_LOOP _Pragma("unroll 1")
+#else
+#define K1_WCHUNK_LOOP _Pragma("unroll")
+#endif
 #ifndef K1_CF_CPOL
 // cache policy of K1's window-coefficient stores (zeroing, direct, flush):
 // 0 default; A/B builds: 2 = nt, 16 = sc1 (write-through, the line leaves
@@ -534,13 +545,14 @@ FFCV_DEV uint32_t make_pair(const TB &T, int slot, int bits, const uint32_t *L, 
 // The first-level index is the top bits of the reader's high word, one
 // shift by the low field (the shifter reads 5 bits).  A slot without a
 // first-level LUT (bits 0) has shift 31 onto two reserved zero words.
-// Write-pass reader: every step issues exactly one buffer load (a lane that
-// does not refill reads out of range: no access, returns 0) and the step
-// then issues exactly three buffer stores (out of range when a lane has
-// nothing to store).  vmcnt counts loads and stores in issue order, so with
-// these static counts the next step waits for its load with vmcnt(3) instead
-// of draining the previous steps' coefficient stores (vmcnt(0), which the
-// conditional global stores forced).
+// Write-pass reader: every AC step and every chunk part (write_range) issues
+// exactly one buffer load (a lane that does not refill reads out of range: no
+// access, returns 0) and then a fixed set of buffer stores (two 2-byte stores
+// in a step; the DC store and three 16-byte stores in a chunk part; out of
+// range when a lane has nothing to store).  vmcnt counts loads and stores in
+// issue order, so with these static counts the next step waits for its load
+// with a counted vmcnt instead of draining the previous steps' coefficient
+// stores (vmcnt(0), which the conditional global stores forced).
 // (BUF_OOR / BUF_CFG: device_common.h)
 struct BufReader {
   __amdgpu_buffer_rsrc_t rs;
@@ -705,9 +717,13 @@ FFCV_DEV DecState sync_range(JShared &S, const TB &T, const uint32_t *words, Dec
 // WRITE decode: DC differences of every block and the AC coefficients (in
 // zigzag order; the IDCT de-zigzags in registers) of the blocks inside the
 // window.  blk = index of the block in progress (z > 0) or of the next block
-// to start (z == 0).  Straight-line like sync_range: the next block's
-// destination and window test are computed from the next phase's
-// descriptor (loaded at the top of the step) and selected at a block end.
+// to start (z == 0).  The loop runs in chunks: a per-chunk part that does
+// everything a block boundary needs (flush of the block that ended in the
+// last chunk, the next block's destination and window test from the next
+// phase's descriptor, the DC symbol), then K1_WCHUNK AC-only steps.  A lane
+// that ends its block or its range inside a chunk idles through the chunk's
+// remaining steps (no bits, out-of-range stores), so the per-block work costs
+// one chunk part per block instead of a share of every step.
 FFCV_DEV void locate_block(const int4 pd0, const int4 pd1, uint32_t blk, uint32_t nblocks, int mx, int my,
                            uint32_t &boff, bool &inwin) {
   // pd0 = {base block, blocks per MCU row, hs, mx_lo}, pd1 = {mx_hi, my_lo, my_hi, component}
@@ -763,52 +779,15 @@ FFCV_DEV void write_range(JShared &S, const TB &T, const uint32_t *words, uint32
   locate_block(S.phr[ph].pd0, S.phr[ph].pd1, blk, nblocks, mx, my, boff, inwin);
   int cc = S.phr[ph].pd1.w;  // component of the block in progress
   int r0 = 0, r1 = 0, r2 = 0;  // running DC sums of the blocks this lane started
-  const bool alive = true;  // (a wave-uniform loop with finished lanes idling measured neutral)
-  while (pos < end_bit && !(z == 0 && blk >= nblocks)) {
+  for (;;) {
     K1_DIAG(iters++);
+    // ---- chunk part: block boundaries (z >= 64: ended in the last chunk; z == 0: a DC is next)
     br.begin();
     const uint32_t ndinf = S.phr[nph].dinf, nainf = S.phr[nph].ainf;
     const int nnph = S.phr[nph].next;
     const int4 npd0 = S.phr[nph].pd0, npd1 = S.phr[nph].pd1;
-    const bool isblk = z == 0 && alive;
-    const uint32_t e = decode_entry(T, S.acmask, z == 0 ? dinf : ainf, br.acc, alive);
-    // see make_pair: vs = this step's bits and z advance
-    const int zi1 = alive ? (int)(e >> 25) : 0;
-    const bool one = z + zi1 >= 64, pair = zi1 != 0;
-    const uint32_t vs = alive ? (one ? e >> 16 : e) : 0u;
-    const int nbits = (int)(vs & 31), zadd = (int)(vs >> 9) & 127;
-    const int t1 = pair ? (int)(e >> 16) & 31 : nbits, zinc = pair ? zi1 : zadd;
-    const uint32_t size = (e >> 5) & 15, size2 = pair && !one ? (e >> 21) & 15 : 0u;
-    // the extra bits sit in the reader's high word (t1, nbits <= 31)
-    const uint32_t hi = (uint32_t)(br.acc >> 32);
-    const int v = huff_value(hi, 32 - t1, size), v2 = huff_value(hi, 32 - nbits, size2);
-    br.consume(nbits);
-    pos += nbits;
-    // three stores every step (see BufReader): DC difference, first and
-    // second AC coefficient, each out of range when the lane has none
-    const uint32_t o1 = (boff + (uint32_t)min(z + zinc - 1, 63)) * 2, o2 = (boff + (uint32_t)min(z + zadd - 1, 63)) * 2;
-    {  // DC: the difference itself (coefficient output) or this lane's running sum
-      const int rsum = (cc == 0 ? r0 : (cc == 1 ? r1 : r2)) + v;
-      r0 = isblk && cc == 0 ? rsum : r0;
-      r1 = isblk && cc == 1 ? rsum : r1;
-      r2 = isblk && cc == 2 ? rsum : r2;
-      if (dc_diffs)
-        __builtin_amdgcn_raw_buffer_store_b16((short)v, drs, isblk ? blk * 2 : BUF_OOR, 0, 0);
-      else if (isblk && inwin)
-        acs16[0] = (int16_t)rsum;  // a DC step starts the block: this lane stages it
-    }
-    const int p1 = min(z + zinc - 1, 63), p2 = min(z + zadd - 1, 63);
-    const bool a1 = z != 0 && size && inwin && alive, a2 = size2 && inwin && alive;
-    const bool l1 = a1 && stg && p1 < ACS_Z, l2 = a2 && stg && p2 < ACS_Z;
-    if (l1) acs16[p1] = (int16_t)v;
-    if (l2) acs16[p2] = (int16_t)v2;
-    // (issuing these under exec masks instead measured 0.6-2% slower: K1's
-    // refill would then wait for every pending store, see BufReader)
-    __builtin_amdgcn_raw_buffer_store_b16((short)v, crs, a1 && !l1 ? o1 : BUF_OOR, 0, K1_CF_CPOL);
-    __builtin_amdgcn_raw_buffer_store_b16((short)v2, crs, a2 && !l2 ? o2 : BUF_OOR, 0, K1_CF_CPOL);
-    z += zadd;
     const bool bend = z >= 64;
-    {  // a staged block that ends leaves as three 16-byte stores
+    {  // a staged block that ended leaves as three 16-byte stores
       const bool fl = bend && stg && inwin;
       // left undefined where the lane does not flush (its stores go out of
       // range): zeroing it cost 12 moves per step
@@ -844,6 +823,56 @@ FFCV_DEV void write_range(JShared &S, const TB &T, const uint32_t *words, uint32
     boff = bend ? nboff : boff;
     inwin = bend ? ninwin : inwin;
     cc = bend ? npd1.w : cc;
+    {  // DC: the difference itself (coefficient output) or this lane's running sum
+      const bool isblk = z == 0 && pos < end_bit && blk < nblocks;
+      const uint32_t e = decode_entry(T, S.acmask, dinf, br.acc, isblk);
+      const int nbits = isblk ? (int)(e & 31) : 0;
+      const int v = huff_value((uint32_t)(br.acc >> 32), 32 - nbits, (e >> 5) & 15);
+      br.consume(nbits);
+      pos += nbits;
+      const int rsum = (cc == 0 ? r0 : (cc == 1 ? r1 : r2)) + v;
+      r0 = isblk && cc == 0 ? rsum : r0;
+      r1 = isblk && cc == 1 ? rsum : r1;
+      r2 = isblk && cc == 2 ? rsum : r2;
+      if (dc_diffs)
+        __builtin_amdgcn_raw_buffer_store_b16((short)v, drs, isblk ? blk * 2 : BUF_OOR, 0, 0);
+      else if (isblk && inwin)
+        acs16[0] = (int16_t)rsum;  // a DC step starts the block: this lane stages it
+      z = isblk ? 1 : z;
+    }
+    if (!(z > 0 && pos < end_bit)) break;  // nothing left in this lane's range
+    // ---- K1_WCHUNK AC-only steps: one refill load and two 2-byte stores each
+    // (see BufReader); no block-end work, the lane idles once z >= 64
+    K1_WCHUNK_LOOP
+    for (int s = 0; s < K1_WCHUNK; s++) {
+      br.begin();
+      const bool live = z < 64 && pos < end_bit;
+      uint32_t e = decode_entry(T, S.acmask, ainf, br.acc, live);
+      e = live ? e : 0u;  // an idle lane: no bits, no advance, sizes 0
+      // see make_pair: vs = this step's bits and z advance
+      const int zi1 = (int)(e >> 25);
+      const bool one = z + zi1 >= 64, pair = zi1 != 0;
+      const uint32_t vs = one ? e >> 16 : e;
+      const int nbits = (int)(vs & 31), zadd = (int)(vs >> 9) & 127;
+      const int t1 = pair ? (int)(e >> 16) & 31 : nbits, zinc = pair ? zi1 : zadd;
+      const uint32_t size = (e >> 5) & 15, size2 = pair && !one ? (e >> 21) & 15 : 0u;
+      // the extra bits sit in the reader's high word (t1, nbits <= 31)
+      const uint32_t hi = (uint32_t)(br.acc >> 32);
+      const int v = huff_value(hi, 32 - t1, size), v2 = huff_value(hi, 32 - nbits, size2);
+      br.consume(nbits);
+      pos += nbits;
+      const int p1 = min(z + zinc - 1, 63), p2 = min(z + zadd - 1, 63);
+      const uint32_t o1 = (boff + (uint32_t)p1) * 2, o2 = (boff + (uint32_t)p2) * 2;
+      const bool a1 = size && inwin, a2 = size2 && inwin;
+      const bool l1 = a1 && stg && p1 < ACS_Z, l2 = a2 && stg && p2 < ACS_Z;
+      if (l1) acs16[p1] = (int16_t)v;
+      if (l2) acs16[p2] = (int16_t)v2;
+      // (issuing these under exec masks instead measured 0.6-2% slower: K1's
+      // refill would then wait for every pending store, see BufReader)
+      __builtin_amdgcn_raw_buffer_store_b16((short)v, crs, a1 && !l1 ? o1 : BUF_OOR, 0, K1_CF_CPOL);
+      __builtin_amdgcn_raw_buffer_store_b16((short)v2, crs, a2 && !l2 ? o2 : BUF_OOR, 0, K1_CF_CPOL);
+      z += zadd;
+    }
   }
   rs0 = r0;
   rs1 = r1;

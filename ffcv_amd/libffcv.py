@@ -296,6 +296,24 @@ def jpeg_scan_stats(images):
     return stats[:n]
 
 
+def cpu_jpeg_coefficients(image):
+    """int16 (blocks, 64): every coded block of one JPEG in scan order, natural
+    order with the absolute DC, from the CPU decoder (a test helper; bound on
+    first use, so that a library of an earlier revision still loads)."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    fn = lib().ffcv_cpu_jpeg_coefficients
+    fn.restype = ctypes.c_int
+    fn.argtypes = [c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]
+    n = ctypes.c_uint64()
+    out = np.zeros((1, 64), np.int16)
+    for cap in (0, None):  # count the blocks, then read them
+        cap = n.value if cap is None else cap
+        out = np.zeros((max(cap, 1), 64), np.int16)
+        if fn(image.ctypes.data, image.size, out.ctypes.data, cap, ctypes.byref(n)):
+            raise RuntimeError(lib().ffcv_last_error().decode(errors='replace'))
+    return out[:n.value]
+
+
 def cpu_decode_batch(images, heights, widths, modes, out: np.ndarray, crops=None, nthreads=1):
     """The reference's per-sample CPU decode loop as one native call
     (ffcv_cpu_decode_batch): images[k] are host uint8 arrays (JPEG bytes or

@@ -9,5 +9,5 @@ mkdir -p build/ab
 OUT=$(pwd)/build/ab/$NAME.so
 cd $T/ffcv_amd/csrc
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -shared -std=c++17 -ffp-contract=off -fno-fast-math \
-  -Wno-unused-function "$@" -o $OUT ffcv_common.hip ffcv_rrc.hip ffcv_jpeg.hip ffcv_host.hip ffcv_cpu_jpeg.hip
+  -Wno-unused-function "$@" -o $OUT ffcv_common.hip ffcv_rrc.hip ffcv_jpeg.hip ffcv_host.hip ffcv_cpu_jpeg.hip ffcv_color.hip
 rm -rf $T

@@ -3,6 +3,8 @@
 //   gcc -O2 -o /tmp/sync_sim tools/sync_sim.c && /tmp/sync_sim file.jpg [lanes] [heur]
 // Prints rounds, the per-round maximum of symbols decoded by a lane (the
 // latency proxy: rounds end at a workgroup barrier) and the total work.
+// heur 12 (`sync_sim file.jpg 64 12`) models the write pass instead: chunks
+// per image for K1_WCHUNK = 1..8 (profiles/k1_wchunk_model.txt).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -273,6 +275,85 @@ int main(int argc, char **argv) {
       }
     }
     printf("symbols %ld steps %ld (%.3f steps/symbol) PB %d MS %d DCP %d\n", nsym, nstep, (double)nstep / nsym, PB, MS, DCP);
+    return 0;
+  }
+  if (heur == 12) {  // write-pass chunks: `sync_sim file.jpg 64 12`
+    // The write pass (write_range) on its converged lane states: a DC symbol
+    // alone in a per-chunk part, then C AC steps per chunk, an AC step taking
+    // two symbols when both (codes + extra bits) fit in PB bits, the first is
+    // not EOB and does not end the block.  A lane that ends a block idles to
+    // the end of its chunk.  Lane ranges: min(lanes, ceil(bits / 192)) equal
+    // bit ranges; a lane starts at the first symbol at or after its range
+    // start and runs to the first symbol at or after its range end.  Prints,
+    // for C = 1..8, the chunks of the slowest lane (the wave runs that many)
+    // and C x chunks, beside the steps of the one-symbol-class-per-step loop
+    // (DC and AC steps together), and the histogram of AC steps per block.
+    const int PB = getenv("SIM_PAIRB") ? atoi(getenv("SIM_PAIRB")) : 11;
+    uint32_t nthr = (tbits + 191) / 192;
+    if (nthr > (uint32_t)lanes) nthr = lanes;
+    if (nthr < 1) nthr = 1;
+    const uint32_t cbits = (tbits + nthr - 1) / nthr;
+    long chunks[9] = {0}, cur[9] = {0}, base = 0, curb = 0, nsym = 0, nblk = 0, hist[65] = {0};
+    uint32_t pos = 0;
+    int z = 0, ph = 0, t = 0, k = 0, whole = 1;  // k: AC steps of the block so far in this lane
+    while (pos < tbits) {
+      while (t + 1 < (int)nthr && pos >= (uint32_t)(t + 1) * cbits) {  // the next lane takes over
+        for (int c = 1; c <= 8; c++) {
+          cur[c] += (k + c - 1) / c;
+          if (cur[c] > chunks[c]) chunks[c] = cur[c];
+          cur[c] = 0;
+        }
+        if (curb > base) base = curb;
+        curb = 0;
+        k = 0;
+        whole = z == 0;
+        t++;
+      }
+      int len, bad;
+      curb++;
+      if (z == 0) {
+        int v = sym(ph_dc[ph], pos, &len, &bad);
+        pos += len + v;
+        z = 1;
+        nsym++;
+        nblk++;
+        continue;
+      }
+      int v = sym(ph_ac[ph], pos, &len, &bad);
+      int sz = v & 15, r = v >> 4, t1 = len + sz;
+      pos += t1;
+      z = sz ? z + r + 1 : (r == 15 ? z + 16 : 64);
+      nsym++;
+      k++;
+      if ((sz || r == 15) && z < 64 && len <= PB && pos < tbits) {  // a second symbol in the same step
+        int v2 = sym(ph_ac[ph], pos, &len, &bad);
+        int sz2 = v2 & 15, r2 = v2 >> 4;
+        if (t1 + len + sz2 <= PB) {
+          pos += len + sz2;
+          z = sz2 ? z + r2 + 1 : (r2 == 15 ? z + 16 : 64);
+          nsym++;
+        }
+      }
+      if (z >= 64) {
+        for (int c = 1; c <= 8; c++) cur[c] += (k + c - 1) / c;
+        if (whole) hist[k > 64 ? 64 : k]++;
+        k = 0;
+        whole = 1;
+        z = 0;
+        ph = (ph + 1) % bpm;
+      }
+    }
+    for (int c = 1; c <= 8; c++) {
+      cur[c] += (k + c - 1) / c;
+      if (cur[c] > chunks[c]) chunks[c] = cur[c];
+    }
+    if (curb > base) base = curb;
+    printf("chunks: blocks %ld symbols %ld lanes %u steps %ld", nblk, nsym, nthr, base);
+    for (int c = 1; c <= 8; c++) printf(" C%d %ld %ld", c, chunks[c], c * chunks[c]);
+    printf("\nacsteps:");
+    for (int q = 0; q <= 64; q++)
+      if (hist[q]) printf(" %d:%ld", q, hist[q]);
+    printf("\n");
     return 0;
   }
   if (heur == 10) {  // phase-probe heuristic: pick the start phase with the fewest implausible
