@@ -24,12 +24,13 @@ c_int = ctypes.c_int
 c_int32 = ctypes.c_int32
 c_uint32 = ctypes.c_uint32
 c_uint64 = ctypes.c_uint64
+c_int64 = ctypes.c_int64
 c_double = ctypes.c_double
 
 # per-sample device status codes (FFCV_SAMPLE_*)
 SAMPLE_STATUS = {0: 'ok', 1: 'bad marker', 2: 'unsupported JPEG feature',
                  3: 'image larger than decoder context', 4: 'corrupt entropy stream',
-                 5: 'geometry mismatch', 6: 'rng stream exhausted'}
+                 5: 'geometry mismatch', 6: 'rng stream exhausted', 7: 'label outside [0, num_classes)'}
 
 
 class FFCVError(RuntimeError):
@@ -150,6 +151,10 @@ _SIGS = {
     'ffcv_color_jitter_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_uint64]),
     'ffcv_color_jitter_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'ffcv_mixup_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int]),
+    'ffcv_mixup_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int,
+                                      c_int]),
+    'ffcv_mixup_onehot_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -525,6 +530,93 @@ def color_jitter_batch_host(images, steps, apply, ratio):
     _check(lib().ffcv_color_jitter_batch_host(_p(images), B, H, W, ctypes.byref(params), _p(apply), _p(ratio)),
            'ffcv_color_jitter_batch_host')
     return images
+
+
+MIXUP_U8, MIXUP_F32 = 1, 2  # FFCV_MIXUP_*
+
+
+def _dense_like(a, b):
+    """True when tensors a and b have the same shape and strides and cover
+    their storage without gaps (contiguous in some permutation of the axes)."""
+    if tuple(a.shape) != tuple(b.shape) or tuple(a.stride()) != tuple(b.stride()):
+        return False
+    expect = 1
+    for size, stride in sorted(((int(n), int(st)) for n, st in zip(a.shape, a.stride()) if n != 1),
+                               key=lambda x: x[1]):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def mixup_batch(inp, out, lam, batch_size, same_lambda, stream=None, run=None):
+    """ImageMixup on a device uint8 or float32 batch (ffcv_mixup_batch):
+    ``out[i] = cast(l * inp[i] + (1 - l) * inp[neighbour])`` in float64, the
+    neighbour being sample i - 1, or the last sample of i's own batch of
+    ``batch_size`` when i is its first.  ``lam``: device float64, one per
+    sample or, with ``same_lambda``, one per batch.  ``inp`` and ``out`` are
+    dense, laid out alike, with the samples outermost in memory (a
+    channels_last view of a dense buffer is fine), and must not overlap.
+    ``run``: diagnostics only, the kernel's run length (1, 2, 4 or 8)."""
+    import torch
+    dt = {torch.uint8: MIXUP_U8, torch.float32: MIXUP_F32}.get(inp.dtype)
+    if dt is None or out.dtype != inp.dtype:
+        raise TypeError(f'mixup_batch: uint8 or float32 tensors of one dtype are required, got {inp.dtype} '
+                        f'and {out.dtype}')
+    n = int(inp.shape[0]) if inp.dim() else 0
+    if inp.dim() < 1 or n < 1 or inp.numel() < 1 or not _dense_like(inp, out) or \
+            int(inp.stride(0)) * n != inp.numel():
+        raise TypeError('mixup_batch: inp and out must be dense tensors of the same shape and strides with the '
+                        f'samples outermost in memory, got shapes {tuple(inp.shape)}, {tuple(out.shape)} and '
+                        f'strides {tuple(inp.stride())}, {tuple(out.stride())}')
+    nb = -(-n // int(batch_size)) if int(batch_size) > 0 else 0
+    if lam.dtype != torch.float64 or not lam.is_contiguous() or lam.numel() < (nb if same_lambda else n):
+        raise TypeError('mixup_batch: lam must be a contiguous float64 tensor with one value per '
+                        + ('batch' if same_lambda else 'sample'))
+    args = (_stream(stream), _p(inp), _p(out), n, inp.numel() // n, dt, int(batch_size), _p(lam),
+            int(bool(same_lambda)))
+    if run is None:
+        _check(lib().ffcv_mixup_batch(*args), 'ffcv_mixup_batch')
+        return out
+    fn = lib().ffcv_mixup_batch_run   # not in ffcv_hip.h: bound on first use
+    fn.restype = c_int
+    fn.argtypes = _SIGS['ffcv_mixup_batch'][1] + [c_int]
+    _check(fn(*args, int(run)), 'ffcv_mixup_batch_run')
+    return out
+
+
+def mixup_batch_host(inp: np.ndarray, out: np.ndarray, lam, batch_size, same_lambda, nthreads=1):
+    """The same on C-contiguous numpy uint8 or float32 arrays (samples along
+    axis 0), compiled from the kernel's pixel function."""
+    dt = {np.dtype(np.uint8): MIXUP_U8, np.dtype(np.float32): MIXUP_F32}.get(inp.dtype)
+    if dt is None or out.dtype != inp.dtype or inp.shape != out.shape or inp.ndim < 1 or inp.size < 1 or \
+            not inp.flags.c_contiguous or not out.flags.c_contiguous:
+        raise TypeError('mixup_batch_host: C-contiguous uint8 or float32 arrays of one shape are required')
+    n = int(inp.shape[0])
+    lam = np.ascontiguousarray(lam, np.float64).reshape(-1)
+    nb = -(-n // int(batch_size)) if int(batch_size) > 0 else 0
+    if lam.size < (nb if same_lambda else n):
+        raise TypeError('mixup_batch_host: lam needs one value per ' + ('batch' if same_lambda else 'sample'))
+    _check(lib().ffcv_mixup_batch_host(_p(inp), _p(out), n, inp.size // n, dt, int(batch_size), _p(lam),
+                                       int(bool(same_lambda)), int(max(1, nthreads))), 'ffcv_mixup_batch_host')
+    return out
+
+
+def mixup_onehot_batch(labels3, out, status, stream=None):
+    """MixupToOneHot in one launch (ffcv_mixup_onehot_batch): labels3 device
+    float32 (n, 3) of (a, b, lam); out device float32 (n, num_classes);
+    status device int32 (n,), nonzero where a label is out of range (that
+    row stays zero)."""
+    import torch
+    n = int(labels3.shape[0]) if labels3.dim() == 2 else -1
+    if labels3.dtype != torch.float32 or out.dtype != torch.float32 or status.dtype != torch.int32 or \
+            labels3.dim() != 2 or int(labels3.shape[1]) != 3 or out.dim() != 2 or int(out.shape[0]) != n or \
+            status.numel() != n or not (labels3.is_contiguous() and out.is_contiguous() and status.is_contiguous()):
+        raise TypeError('mixup_onehot_batch: contiguous float32 (n, 3) labels, float32 (n, num_classes) out and '
+                        'int32 (n,) status are required')
+    _check(lib().ffcv_mixup_onehot_batch(_stream(stream), _p(labels3), _p(out), n, int(out.shape[1]), _p(status)),
+           'ffcv_mixup_onehot_batch')
+    return out
 
 
 def scratch_bound(heights, widths, nbytes):

@@ -19,7 +19,10 @@ What changed for MI355X:
   and the consumer receives them one batch at a time (views of that set).
   Three sets rotate (two launches in flight while the consumer reads the
   third), on three streams, which HIP's default 4 hardware queues hold.
-  Graphs with batch-level operations (mixup, user ops) keep G = 1.
+  Batch-level operations that declare ``per_batch`` (the mixup operations)
+  keep the group: each context carries the Loader's batch size
+  (``launch_batch_size``) and they cut the launch at its multiples.  Graphs
+  with any other batch-level operation (unknown user ops) keep G = 1.
 * Buffer sets are released by the consumer: ``__next__`` records an event on
   the consumer stream once the previous set's last batch has been handed
   out; the producer waits (host side) for that release before re-using a
@@ -167,6 +170,7 @@ class EpochIterator(threading.Thread):
         for c in self.contexts:
             c.host_state = self.storage_state
             c.loader_seed = loader.seed
+            c.launch_batch_size = loader.batch_size  # c.batch_size is the launch capacity G * batch_size
         if self.is_cuda:  # reused buffers: order this epoch after the consumer's queued work
             ev = ch.cuda.Event()
             ev.record(self.current_stream)

@@ -110,8 +110,9 @@ class Loader:
         batch's bytes through pinned memory.
     batches_per_launch : int, optional (keyword only, new)
         Consecutive batches decoded by one launch sequence when every
-        operation is per-sample (default: enough batches for ~6k samples,
-        which fills the MI355X; 1 when the graph mixes samples).
+        operation is per-sample, or per-batch like the mixup operations
+        (default: enough batches for ~12k samples, which fills the MI355X;
+        1 when the graph holds any other batch-level operation).
     entropy_index : bool (keyword only, new)
         With ``device_cache``: keep, per JPEG field, 768 bytes of HBM per
         sample recording where each lane range of the parallel Huffman

@@ -331,11 +331,14 @@ class Graph:
         return self.exec_nodes, [self.outputs[k].id for k in self.leaf_nodes]
 
     def groupable(self):
-        """True when every operation treats samples independently, so that
-        consecutive batches may run through the graph as one launch."""
+        """True when every operation treats samples independently
+        (``per_sample``) or mixes them only within one batch and handles a
+        launch of several batches itself (``per_batch``), so that consecutive
+        batches may run through the graph as one launch."""
         if not self._finalized:
             self.collect_requirements()
-        return all(getattr(n.operation, 'per_sample', False) for n in self.exec_nodes)
+        return all(getattr(n.operation, 'per_sample', False) or getattr(n.operation, 'per_batch', False)
+                   for n in self.exec_nodes)
 
     def allocation_signature(self):
         """The allocations in execution order, independent of node ids."""

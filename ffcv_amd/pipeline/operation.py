@@ -13,10 +13,18 @@ Operations that know how to run on a HIP device set the class attribute
 front of any other operation that receives device-resident data.
 
 ``per_sample = True`` declares that the operation treats every sample of a
-batch independently (no batch-level mixing such as ImageMixup): the
-EpochIterator may then run several consecutive batches through the graph as
-one launch (one decode launch fills the GPU) and hand them out one by one.
-Unknown user operations default to False, which keeps one batch per run.
+batch independently: the EpochIterator may then run several consecutive
+batches through the graph as one launch (one decode launch fills the GPU)
+and hand them out one by one.
+
+``per_batch = True`` declares a batch-level operation that keeps launch
+groups: it mixes samples only within one batch and handles a launch of
+several batches itself, by cutting its input at multiples of the Loader's
+batch size (``runtime.current().launch_batch_size``).  ImageMixup and
+LabelMixup are such operations.
+
+Unknown user operations default to False for both, which keeps one batch per
+run.
 """
 from abc import ABC, abstractmethod
 from typing import TYPE_CHECKING, Callable, Optional, Tuple
@@ -33,6 +41,7 @@ if TYPE_CHECKING:
 class Operation(ABC):
     device_aware = False
     per_sample = False
+    per_batch = False
 
     def __init__(self):
         self.metadata: np.ndarray = None

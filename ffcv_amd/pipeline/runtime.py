@@ -118,7 +118,8 @@ class BatchContext:
         self.dataset = dataset
         self.loader_seed = loader_seed
         self.slot = slot
-        self.batch_size = batch_size
+        self.batch_size = batch_size          # launch capacity: G * the Loader's batch size
+        self.launch_batch_size = None         # the Loader's batch size (None outside a Loader: one batch)
         self.epoch = 0
         self.stream = None
         self.batch_ids = None      # device int64[B]
@@ -180,6 +181,30 @@ class BatchContext:
                 done_event = ch.cuda.Event()
                 done_event.record(self.stream)
             self._h2d_done = done_event
+
+    def pinned_f64(self, key, n):
+        """float64[>= n] of this slot, for per-batch host draws (mixup's
+        lambdas): (numpy view of the pinned host buffer, the pinned tensor,
+        its device twin).  The host buffer is guarded like ``_ids_host``: it
+        is written only after the copies of the slot's previous batch are
+        done (``_wait_host_buffers``), and ``end_batch`` records the event
+        that covers this batch's copy."""
+        self._wait_host_buffers()
+        buf = self._staging.get(key)
+        if buf is None or buf[1].numel() < n:
+            cap = max(int(n), self.batch_size)
+            host = ch.empty(cap, dtype=ch.float64).pin_memory()
+            buf = (host.numpy(), host, ch.empty(cap, dtype=ch.float64, device=self.dataset.device))
+            self._staging[key] = buf
+        return buf
+
+    def device_buffer(self, key, n, dtype):
+        """A device tensor of n elements that this slot keeps (stream order
+        makes its reuse by the slot's next batch safe)."""
+        buf = self._staging.get(key)
+        if buf is None or buf.numel() < n:
+            buf = self._staging[key] = ch.empty(int(n), dtype=dtype, device=self.dataset.device)
+        return buf
 
     def status_host(self, i, like):
         buf = self._status_host.get(i)

@@ -50,7 +50,8 @@ enum {
   FFCV_SAMPLE_TOO_LARGE = 3,       /* exceeds the ctx's max size or scratch arena */
   FFCV_SAMPLE_CORRUPT = 4,         /* entropy stream inconsistent */
   FFCV_SAMPLE_GEOMETRY = 5,        /* SOF size != .beton metadata */
-  FFCV_SAMPLE_RNG = 6              /* > 623 MT19937 draws for one stream */
+  FFCV_SAMPLE_RNG = 6,             /* > 623 MT19937 draws for one stream */
+  FFCV_SAMPLE_LABEL = 7            /* MixupToOneHot: label outside [0, num_classes) */
 };
 
 /* One sample of a batch, as resolved from the .beton metadata + allocation
@@ -502,6 +503,45 @@ int ffcv_color_jitter_batch_host(uint8_t *images, int batch, int height,
                                  int width,
                                  const ffcv_color_jitter_params *params,
                                  const uint8_t *apply, const double *ratio);
+
+/* --------------------------------------------------------- mixup ------ */
+/* mixup.py: ImageMixup.  Sample i of a dense [n_samples][sample_elems] array
+ * belongs to batch s = i / batch_size, of length min(batch_size, n_samples -
+ * s * batch_size); its neighbour is sample i - 1, or the LAST sample of its
+ * own batch when i is the batch's first (a batch of one mixes a sample with
+ * itself).  With l = lam[s] when same_lambda, else lam[i]:
+ *   out[i][j] = cast(l * double(in[i][j]) + (1 - l) * double(in[nb][j]))
+ * in float64, every multiply and add rounded on its own (never fused); the
+ * cast truncates for uint8 (the value lies in [0, 255 + 3e-14]) and rounds to
+ * nearest even for float32.  A launch of several batches is one call.
+ *   in, out : device, aligned to the element size only (a uint8 batch may
+ *             start at any byte); the two ranges must not overlap
+ *   lam     : device float64, one per sample, or one per batch when
+ *             same_lambda
+ * FFCV_EINVAL, before any launch, for a null pointer, a count <= 0, an
+ * unknown dtype or overlapping ranges. */
+enum {
+  FFCV_MIXUP_U8 = 1,
+  FFCV_MIXUP_F32 = 2
+};
+int ffcv_mixup_batch(void *stream, const void *in, void *out,
+                     int64_t n_samples, int64_t sample_elems, int dtype,
+                     int64_t batch_size, const double *lam, int same_lambda);
+/* The same on host memory (lam on the host too), compiled from the same
+ * pixel function as the kernel, over nthreads threads (one sample at a
+ * time each). */
+int ffcv_mixup_batch_host(const void *in, void *out, int64_t n_samples,
+                          int64_t sample_elems, int dtype, int64_t batch_size,
+                          const double *lam, int same_lambda, int nthreads);
+/* mixup.py: MixupToOneHot in one launch.  labels3 is device float32 [n][3]
+ * of (label a, label b, lam) as LabelMixup writes it and is not changed;
+ * out is device float32 [n][num_classes]: zeros, then out[i][a] = lam, then
+ * out[i][b] = float(1) - lam (the second store wins when a == b).  A row
+ * with a label outside [0, num_classes) stays zero and gets status[i] =
+ * FFCV_SAMPLE_LABEL; every other status[i] is FFCV_SAMPLE_OK.
+ *   status : device int32[n], required */
+int ffcv_mixup_onehot_batch(void *stream, const float *labels3, float *out,
+                            int64_t n, int64_t num_classes, int32_t *status);
 
 #ifdef __cplusplus
 }
