@@ -26,6 +26,7 @@ c_uint32 = ctypes.c_uint32
 c_uint64 = ctypes.c_uint64
 c_int64 = ctypes.c_int64
 c_double = ctypes.c_double
+c_float = ctypes.c_float
 
 # per-sample device status codes (FFCV_SAMPLE_*)
 SAMPLE_STATUS = {0: 'ok', 1: 'bad marker', 2: 'unsupported JPEG feature',
@@ -155,6 +156,12 @@ _SIGS = {
     'ffcv_mixup_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int,
                                       c_int]),
     'ffcv_mixup_onehot_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    'ffcv_poison_batch': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                  c_void_p, c_float, c_float]),
+    'ffcv_poison_batch_host': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_float, c_float, c_int]),
+    'ffcv_replace_label_batch': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                         c_int64]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -617,6 +624,85 @@ def mixup_onehot_batch(labels3, out, status, stream=None):
     _check(lib().ffcv_mixup_onehot_batch(_stream(stream), _p(labels3), _p(out), n, int(out.shape[1]), _p(status)),
            'ffcv_mixup_onehot_batch')
     return out
+
+
+def _device_ids(who, sample_ids, poison_ids, n, device):
+    import torch
+    if sample_ids.dtype != torch.int64 or poison_ids.dtype != torch.int64 or sample_ids.numel() != n or \
+            poison_ids.dim() != 1 or not (sample_ids.is_contiguous() and poison_ids.is_contiguous()) or \
+            sample_ids.device != device or poison_ids.device != device:
+        raise TypeError(f'{who}: sample_ids must be a contiguous int64 tensor with one id per sample and poison_ids '
+                        'a contiguous 1-D int64 tensor of sorted unique non-negative ids, both on the data\'s device')
+
+
+def poison_batch(images, sample_ids, poison_ids, keep, add, clamp=(0, 255), stream=None, form=None):
+    """Poison in place on a device uint8 batch (ffcv_poison_batch): every
+    sample whose id in ``sample_ids`` is one of the sorted ``poison_ids``
+    becomes ``uint8(clip(float32(float32(v * keep) + add), *clamp))``.
+    ``images`` is C-contiguous with the samples along axis 0 (``keep`` and
+    ``add``, device float64, follow a sample's element order); the ids are
+    device int64.  ``form``: diagnostics only, the kernel's (bytes per thread,
+    run length, workgroups ordered by table chunk)."""
+    import torch
+    n = int(images.shape[0]) if images.dim() else 0
+    if images.dtype != torch.uint8 or images.device.type != 'cuda' or n < 1 or images.numel() < 1 or \
+            not images.is_contiguous():
+        raise TypeError('poison_batch: a C-contiguous uint8 device tensor with the samples along axis 0 is required, '
+                        f'got {images.dtype} {tuple(images.shape)} with strides {tuple(images.stride())}')
+    elems = images.numel() // n
+    _device_ids('poison_batch', sample_ids, poison_ids, n, images.device)
+    for t in (keep, add):
+        if t.dtype != torch.float64 or t.numel() != elems or not t.is_contiguous() or t.device != images.device:
+            raise TypeError('poison_batch: keep and add must be contiguous float64 device tensors of one sample\'s '
+                            f'{elems} elements')
+    args = (_stream(stream), _p(images), n, elems, _p(sample_ids), _p(poison_ids), int(poison_ids.numel()), _p(keep),
+            _p(add), float(np.float32(clamp[0])), float(np.float32(clamp[1])))
+    if form is None:
+        _check(lib().ffcv_poison_batch(*args), 'ffcv_poison_batch')
+        return images
+    fn = lib().ffcv_poison_batch_form   # not in ffcv_hip.h: bound on first use
+    fn.restype = c_int
+    fn.argtypes = _SIGS['ffcv_poison_batch'][1] + [c_int, c_int, c_int]
+    _check(fn(*args, int(form[0]), int(form[1]), int(bool(form[2]))), 'ffcv_poison_batch_form')
+    return images
+
+
+def poison_batch_host(images: np.ndarray, sample_ids, poison_ids, keep, add, clamp=(0, 255), nthreads=1):
+    """The same in place on a C-contiguous numpy uint8 array (samples along
+    axis 0), compiled from the kernel's membership and pixel functions.
+    ``poison_ids``: sorted unique ids (uint64)."""
+    if not isinstance(images, np.ndarray) or images.dtype != np.uint8 or images.ndim < 1 or images.size < 1 or \
+            not images.flags.c_contiguous or not images.flags.writeable:
+        raise TypeError('poison_batch_host: a writeable C-contiguous uint8 array is required')
+    n = int(images.shape[0])
+    elems = images.size // n
+    sample_ids = np.ascontiguousarray(sample_ids).astype(np.int64, copy=False).reshape(-1)
+    poison_ids = np.ascontiguousarray(poison_ids, np.uint64).reshape(-1)
+    keep = np.ascontiguousarray(keep, np.float64).reshape(-1)
+    add = np.ascontiguousarray(add, np.float64).reshape(-1)
+    if sample_ids.size != n or keep.size != elems or add.size != elems:
+        raise TypeError(f'poison_batch_host: {n} sample ids and keep / add tables of {elems} values are required, '
+                        f'got {sample_ids.size}, {keep.size} and {add.size}')
+    _check(lib().ffcv_poison_batch_host(_p(images), n, elems, _p(sample_ids), _p(poison_ids), int(poison_ids.size),
+                                        _p(keep), _p(add), float(np.float32(clamp[0])), float(np.float32(clamp[1])),
+                                        int(max(1, nthreads))), 'ffcv_poison_batch_host')
+    return images
+
+
+def replace_label_batch(labels, sample_ids, poison_ids, new_label, stream=None):
+    """ReplaceLabel in place on a contiguous device int64 tensor with one row
+    per sample (ffcv_replace_label_batch); ids as for poison_batch."""
+    import torch
+    n = int(labels.shape[0]) if labels.dim() else 0
+    if labels.dtype != torch.int64 or labels.device.type != 'cuda' or n < 1 or labels.numel() < 1 or \
+            not labels.is_contiguous():
+        raise TypeError(f'replace_label_batch: a contiguous int64 device tensor is required, got {labels.dtype} '
+                        f'{tuple(labels.shape)}')
+    _device_ids('replace_label_batch', sample_ids, poison_ids, n, labels.device)
+    _check(lib().ffcv_replace_label_batch(_stream(stream), _p(labels), n, labels.numel() // n, _p(sample_ids),
+                                          _p(poison_ids), int(poison_ids.numel()), int(new_label)),
+           'ffcv_replace_label_batch')
+    return labels
 
 
 def scratch_bound(heights, widths, nbytes):

@@ -3,6 +3,8 @@ from .flip import RandomHorizontalFlip
 from .translate import RandomTranslate
 from .color_jitter import RandomBrightness, RandomContrast, RandomSaturation
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
+from .poison import Poison
+from .replace_label import ReplaceLabel
 from .ops import ToTensor, ToDevice, ToTorchImage, Convert, View
 from .normalize import NormalizeImage
 from .module import ModuleWrapper
@@ -11,4 +13,4 @@ from .common import Squeeze
 __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 'Squeeze', 'View',
            'RandomHorizontalFlip', 'RandomTranslate', 'Cutout', 'ModuleWrapper',
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
-           'ImageMixup', 'LabelMixup', 'MixupToOneHot']
+           'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']

@@ -543,6 +543,47 @@ int ffcv_mixup_batch_host(const void *in, void *out, int64_t n_samples,
 int ffcv_mixup_onehot_batch(void *stream, const float *labels3, float *out,
                             int64_t n, int64_t num_classes, int32_t *status);
 
+/* -------------------------------------------- poison, replace label ---- */
+/* poisoning.py: Poison.  Every sample i of a dense uint8
+ * [n_samples][sample_elems] array whose dataset index sample_ids[i] is in
+ * the sorted set poison_ids is changed in place, element e to
+ *   t1 = float32(float64(v) * keep[e])
+ *   t2 = float32(float64(t1) + add[e])
+ *   uint8(int(min(max(t2, clamp_lo), clamp_hi)))
+ * which is numpy's `temp *= 1 - alpha; temp += mask * alpha; clip` on a
+ * float32 temp with keep = float64(1 - alpha), add = float64(mask) * alpha.
+ * Every other sample is neither read nor written.  Membership is decided on
+ * the device: no host work and no copy per call.
+ *   images     : device uint8 at any byte alignment
+ *   sample_ids : device int64[n_samples] (a negative id is in no set)
+ *   poison_ids : device uint64[n_poison], sorted, unique
+ *   keep, add  : device float64[sample_elems] each, finite
+ * n_poison == 0 returns FFCV_OK without a launch.  FFCV_EINVAL, before any
+ * launch, for a null pointer, n_samples or sample_elems <= 0, n_poison < 0,
+ * sizes that overflow, ids or tables not aligned to 8 bytes, a clamp outside
+ * 0 <= clamp_lo <= clamp_hi <= 255 and a launch of more than 2^31 - 1
+ * workgroups. */
+int ffcv_poison_batch(void *stream, uint8_t *images, int64_t n_samples,
+                      int64_t sample_elems, const int64_t *sample_ids,
+                      const uint64_t *poison_ids, int64_t n_poison,
+                      const double *keep, const double *add, float clamp_lo,
+                      float clamp_hi);
+/* The same on host memory (ids and tables on the host too), compiled from
+ * the same membership and pixel functions as the kernel, over nthreads
+ * threads (one sample at a time each). */
+int ffcv_poison_batch_host(uint8_t *images, int64_t n_samples,
+                           int64_t sample_elems, const int64_t *sample_ids,
+                           const uint64_t *poison_ids, int64_t n_poison,
+                           const double *keep, const double *add,
+                           float clamp_lo, float clamp_hi, int nthreads);
+/* replace_label.py: ReplaceLabel.  Row i of the device int64
+ * [n][row_elems] labels becomes new_label where sample_ids[i] is in
+ * poison_ids (ids as above); the other rows are not touched. */
+int ffcv_replace_label_batch(void *stream, int64_t *labels, int64_t n,
+                             int64_t row_elems, const int64_t *sample_ids,
+                             const uint64_t *poison_ids, int64_t n_poison,
+                             int64_t new_label);
+
 #ifdef __cplusplus
 }
 #endif
