@@ -225,12 +225,17 @@ const char *parse(const uint8_t *b, size_t n, Dec &d) {
 }
 
 // Entropy-coded segment reader: 0xFF00 de-stuffing; at a marker it feeds
-// zeros (jdhuff.c jpeg_fill_bit_buffer after a marker).
+// zeros (jdhuff.c jpeg_fill_bit_buffer after a marker).  Once a symbol has
+// taken one of those zero bits the data is insufficient: libjpeg finishes
+// the MCU in progress on zeros and leaves every later MCU of the restart
+// interval zero (decode_mcu's insufficient_data), and so does decode_scan.
 struct Bits {
   const uint8_t *p, *end;
   uint64_t acc = 0;  // valid bits left-aligned
   int n = 0;
   bool marker = false;
+  int zbits = 0;  // the last zbits of the n buffered bits are fed zeros
+  bool insufficient = false;
   void fill() {
     // fast path: 8 bytes with no 0xFF among them enter whole
     if (!marker && end - p >= 8) {
@@ -248,20 +253,24 @@ struct Bits {
     }
     while (n <= 56) {
       int v = 0;
+      bool fed = true;  // a zero fed in place of data
       if (!marker && p < end) {
         v = *p;
         if (v == 0xFF) {
           const int nx = p + 1 < end ? p[1] : 0xD9;
           if (nx == 0x00) {
             p += 2;
+            fed = false;
           } else {
             marker = true;
             v = 0;
           }
         } else {
           p++;
+          fed = false;
         }
       }
+      zbits += fed ? 8 : 0;
       acc |= (uint64_t)v << (56 - n);
       n += 8;
     }
@@ -273,6 +282,10 @@ struct Bits {
   void skip(int k) {
     acc <<= k;
     n -= k;
+    if (n < zbits) {
+      insufficient = true;
+      zbits = n;
+    }
   }
   int get(int k) {  // k in 1..16
     if (n < k) fill();
@@ -282,23 +295,36 @@ struct Bits {
   }
   // process_restart: drop the buffered bits, then jdmarker.c next_marker:
   // discard bytes up to the next marker (stuffed FF00 pairs included) and
-  // step over it when it is the RSTn
+  // step over it when it is the RSTn, which makes the data sufficient again.
+  // Any other marker (or the end of the data) stays unread: the reader goes
+  // on feeding zeros, and later restarts find the same marker.
   void restart() {
     acc = 0;
     n = 0;
+    zbits = 0;
     const uint8_t *q = p;
     for (;;) {
       while (q < end && *q != 0xFF) q++;
+      const uint8_t *ff = q;
       while (q < end && *q == 0xFF) q++;
-      if (q >= end) break;
+      if (q >= end) {
+        p = end;
+        marker = true;
+        return;
+      }
       if (*q != 0) {
-        if (*q >= 0xD0 && *q <= 0xD7) q++;
-        break;
+        if (*q >= 0xD0 && *q <= 0xD7) {
+          p = q + 1;
+          marker = false;
+          insufficient = false;
+        } else {
+          p = ff;
+          marker = true;
+        }
+        return;
       }
       q++;
     }
-    p = q;
-    marker = false;
   }
 };
 
@@ -462,6 +488,7 @@ void decode_scan(const uint8_t *b, const Dec &d, Emit &&emit, uint64_t *nsym = n
       }
       left--;
     }
+    const bool skip_mcu = br.insufficient;  // (tested once per MCU, like decode_mcu)
     for (int si = 0; si < d.nc; si++) {
       const int ci = d.scan[si];
       const Comp &c = d.c[ci];
@@ -471,6 +498,10 @@ void decode_scan(const uint8_t *b, const Dec &d, Emit &&emit, uint64_t *nsym = n
         for (int xx = 0; xx < nh; xx++) {
           const int bx = single ? m % sbw : (m % mcux) * c.h + xx, by = single ? m / sbw : (m / mcux) * c.v + yy;
           std::memset(blk, 0, sizeof(blk));
+          if (skip_mcu) {
+            emit(ci, bx, by, blk);
+            continue;
+          }
           int s = decode_sym(br, hd);
           if (s) s = extend(br.get(s), s);
           pred[ci] += s;

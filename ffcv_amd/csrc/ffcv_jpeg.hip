@@ -1172,7 +1172,8 @@ FFCV_DEV int parse_header(JShared &S, const uint8_t *src, uint32_t nbytes, const
       int o = 0;
       while (o < sl) {
         int pq = B(s + o) >> 4, tq = B(s + o) & 15;
-        if (tq > 3) return FFCV_SAMPLE_BAD_MARKER;
+        // (a table must end inside its segment: jdmarker.c get_dqt's JERR_BAD_LENGTH)
+        if (tq > 3 || o + 1 + (pq ? 128 : 64) > sl) return FFCV_SAMPLE_BAD_MARKER;
         S.dqt_off[tq] = s + o + 1;
         S.dqt_prec[tq] = pq;
         S.dqt_ok[tq] = 1;
@@ -1182,26 +1183,30 @@ FFCV_DEV int parse_header(JShared &S, const uint8_t *src, uint32_t nbytes, const
       int o = 0;
       while (o < sl) {
         int tc = B(s + o) >> 4, th = B(s + o) & 15;
-        if (th > 3 || tc > 1) return FFCV_SAMPLE_BAD_MARKER;
+        // (the counts, then the symbols, must end inside the segment: get_dht)
+        if (th > 3 || tc > 1 || o + 17 > sl) return FFCV_SAMPLE_BAD_MARKER;
         int total = 0;
         for (int l = 0; l < 16; l++) total += B(s + o + 1 + l);
-        if (total > 256) return FFCV_SAMPLE_BAD_MARKER;
+        if (total > 256 || o + 17 + total > sl) return FFCV_SAMPLE_BAD_MARKER;
         S.dht_off[tc * 4 + th] = s + o + 1;
         S.dht_ok[tc * 4 + th] = 1;
         o += 17 + total;
       }
     } else if (m == 0xC0 || m == 0xC1) {
+      if (sl < 6) return FFCV_SAMPLE_BAD_MARKER;
       if (B(s) != 8) return FFCV_SAMPLE_UNSUPPORTED;
       S.H = R16(s + 1);
       S.W = R16(s + 3);
       S.ncomp = B(s + 5);
       if (S.ncomp != 1 && S.ncomp != 3) return FFCV_SAMPLE_UNSUPPORTED;
+      if (sl < 6 + 3 * S.ncomp) return FFCV_SAMPLE_BAD_MARKER;
       S.hmax = S.vmax = 1;
       for (int c = 0; c < S.ncomp; c++) {
         S.cid[c] = B(s + 6 + 3 * c);
         S.hs[c] = B(s + 7 + 3 * c) >> 4;
         S.vs[c] = B(s + 7 + 3 * c) & 15;
-        S.tq[c] = B(s + 8 + 3 * c) & 3;
+        if (B(s + 8 + 3 * c) > 3) return FFCV_SAMPLE_BAD_MARKER;  // no such table (JERR_NO_QUANT_TABLE)
+        S.tq[c] = B(s + 8 + 3 * c);
         if (S.hs[c] < 1 || S.hs[c] > 4 || S.vs[c] < 1 || S.vs[c] > 4) return FFCV_SAMPLE_UNSUPPORTED;
         S.hmax = max(S.hmax, S.hs[c]);
         S.vmax = max(S.vmax, S.vs[c]);
@@ -1210,6 +1215,7 @@ FFCV_DEV int parse_header(JShared &S, const uint8_t *src, uint32_t nbytes, const
     } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
       return FFCV_SAMPLE_UNSUPPORTED;  // progressive / lossless / arithmetic
     } else if (m == 0xDD) {
+      if (sl < 2) return FFCV_SAMPLE_BAD_MARKER;
       S.restart = R16(s);
     } else if (m == 0xE0) {
       if (sl >= 5 && B(s) == 'J' && B(s + 1) == 'F' && B(s + 2) == 'I' && B(s + 3) == 'F' && B(s + 4) == 0)
@@ -1221,8 +1227,10 @@ FFCV_DEV int parse_header(JShared &S, const uint8_t *src, uint32_t nbytes, const
       }
     } else if (m == 0xDA) {
       if (!have_sof) return FFCV_SAMPLE_BAD_MARKER;
+      if (sl < 1) return FFCV_SAMPLE_BAD_MARKER;
       int ns = B(s);
       if (ns != S.ncomp) return FFCV_SAMPLE_UNSUPPORTED;  // multi-scan sequential
+      if (sl < 1 + 2 * ns) return FFCV_SAMPLE_BAD_MARKER;
       int order[3];
       for (int i = 0; i < ns; i++) {
         int c = -1;
@@ -1646,7 +1654,15 @@ FFCV_DEV bool entropy_passes(JShared &S, const TB &T, const JpegArgs &a, int k, 
     int64_t cur = g.z == 0 ? (int64_t)blk_base : (int64_t)blk_base - 1;
     bad_lane = cur < 0 || (cur % S.bpm) != g.ph;  // inconsistent stream
   }
-  const bool any_bad = seg_any(bad_lane, sg);
+  // A stream that ends before its last block does (truncated data, an early
+  // marker) is corrupt too: libjpeg pads it with zero bits and leaves the
+  // remaining MCUs grey, this path reports it.  Blocks started, less the one
+  // the last lane range left unfinished (the pad bits of a whole stream may
+  // start one block more).
+  const uint32_t nstarted = seg_read(blk_base + my_cnt, JL - 1, sg);
+  const uint32_t zlast = seg_read((uint32_t)e.z, (int)wuni(nthr - 1), sg);
+  const bool is_short = nstarted - (zlast != 0 ? 1u : 0u) < (uint32_t)S.nblocks;
+  const bool any_bad = seg_any(bad_lane, sg) || is_short;
   if (rec && !any_bad) {  // publish this sample's converged lane states
     const int64_t cur = g.z == 0 ? (int64_t)blk_base : (int64_t)blk_base - 1;
     uint32_t w0 = active ? g.pos : 0u, w1 = active ? (uint32_t)g.z | ((uint32_t)g.ph << 8) : 0u,
@@ -1899,6 +1915,10 @@ __global__ void __launch_bounds__(JW * JT) __attribute__((amdgpu_waves_per_eu(K1
       uint64_t bytes = (uint64_t)smp.height * smp.width * 3;
       uint8_t *o = (uint8_t *)a.out + a.out_stride * k;
       for (uint64_t i = t; i < bytes && i < a.out_stride; i += JL) o[i] = 0;
+    }
+    if (MODE == JM_COEF) {  // the image's whole row of blocks
+      uint4 *o = (uint4 *)((uint8_t *)a.out + a.out_stride * k);
+      for (uint64_t i = t; i < a.out_stride / 16; i += JL) o[i] = make_uint4(0, 0, 0, 0);
     }
   };
 
@@ -2161,6 +2181,12 @@ __global__ void __launch_bounds__(JW * JT) __attribute__((amdgpu_waves_per_eu(K1
                              : entropy_passes(S, *gt, a, k, t, sg, words, total_bits, coef, dcd, sid, MODE == JM_COEF);
   wsync_mem();
   K1_STOP_AT(5, !any_bad);  // diagnostics: K1 up to the write pass
+  if (any_bad) {  // a failed sample like any other: its status, zero output, no K1b / K2 work
+    if (t == 0) S.status = FFCV_SAMPLE_CORRUPT;
+    wsync_lds();
+    fail();
+    return;
+  }
 
   // ------------------------------------------------------------- P6 ----
   // DC prediction (jdhuff.c last_dc_val) for the coefficient output (JM_COEF;

@@ -48,7 +48,7 @@ enum {
   FFCV_SAMPLE_BAD_MARKER = 1,      /* not a JPEG / truncated header */
   FFCV_SAMPLE_UNSUPPORTED = 2,     /* progressive, arithmetic, 12-bit, DRI, CMYK */
   FFCV_SAMPLE_TOO_LARGE = 3,       /* exceeds the ctx's max size or scratch arena */
-  FFCV_SAMPLE_CORRUPT = 4,         /* entropy stream inconsistent */
+  FFCV_SAMPLE_CORRUPT = 4,         /* entropy stream inconsistent, or ends before its last block */
   FFCV_SAMPLE_GEOMETRY = 5,        /* SOF size != .beton metadata */
   FFCV_SAMPLE_RNG = 6,             /* > 623 MT19937 draws for one stream */
   FFCV_SAMPLE_LABEL = 7            /* MixupToOneHot: label outside [0, num_classes) */

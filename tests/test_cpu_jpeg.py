@@ -38,8 +38,9 @@ def test_cpu_imdecode_matches_libjpeg_turbo(hip_lib, oracle):
     from ffcv_amd import libffcv as L
     rng = np.random.default_rng(41)
     imgs, blobs = _set(rng, 56)
-    # restart intervals (DRI + RSTn every 1 / 3 MCUs or every MCU row), and
-    # 4:1:1 / 4:4:0 style layouts Pillow writes with explicit factors
+    # restart intervals: DRI + RSTn every 1 / 3 / 7 MCUs at 4:2:0, and every
+    # MCU row at 4:4:4, 4:2:2 and 4:2:0 (Pillow's subsampling 0, 1, 2); the
+    # 4:1:1 / 4:4:0 / 1x4 layouts are in tests/test_jpeg_container.py
     extra = []
     for k in range(6):
         h, w = imagenet_like_shape(rng, 200)
