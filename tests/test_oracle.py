@@ -5,9 +5,11 @@
 * JPEG: bit-exact against libjpeg-turbo 3.1.4 (Pillow-bundled) driven with
   the reference's TurboJPEG settings (ifast + fancy upsampling, RGB) through
   oracle/ljt_harness.c, and (islow) against Pillow's own decode.
-* INTER_AREA: OpenCV is absent (parity unpinned beyond invariants): the
-  reference's constant-image invariant (test_rrc.py:63), copy at scale 1,
-  exact block means at integer scales.
+* INTER_AREA: OpenCV is absent, so its binary stays unpinned; the semantics
+  of all four kinds are pinned to exact arithmetic within derived bounds in
+  tests/test_resize_exact.py.  Here: the reference's constant-image
+  invariant (test_rrc.py:63), copy at scale 1, exact block means at integer
+  scales.
 """
 import io
 import os
