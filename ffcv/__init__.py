@@ -10,10 +10,7 @@ User code written for the reference keeps its imports unchanged::
 
 Every ``ffcv.<path>`` module is the same module object as
 ``ffcv_amd.<path>`` (a meta-path finder aliases them; nothing is copied),
-so classes and isinstance checks agree between the two names.  Fields the
-reference keeps in their own modules map to where this package defines
-them (NDArray / TorchTensor / JSON descriptors live in
-``ffcv_amd.fields.unsupported``).
+so classes and isinstance checks agree between the two names.
 """
 import importlib
 import importlib.abc
@@ -21,10 +18,7 @@ import importlib.util
 import sys
 
 _IMPL = 'ffcv_amd'
-_RENAMED = {
-    'ffcv.fields.ndarray': 'ffcv_amd.fields.unsupported',
-    'ffcv.fields.json': 'ffcv_amd.fields.unsupported',
-}
+_RENAMED = {}  # reference modules that live under another name here: none
 
 
 def _target(fullname):

@@ -31,7 +31,8 @@ c_float = ctypes.c_float
 # per-sample device status codes (FFCV_SAMPLE_*)
 SAMPLE_STATUS = {0: 'ok', 1: 'bad marker', 2: 'unsupported JPEG feature',
                  3: 'image larger than decoder context', 4: 'corrupt entropy stream',
-                 5: 'geometry mismatch', 6: 'rng stream exhausted', 7: 'label outside [0, num_classes)'}
+                 5: 'geometry mismatch', 6: 'rng stream exhausted', 7: 'label outside [0, num_classes)',
+                 8: 'sample index or row outside the dataset bytes'}
 
 
 class FFCVError(RuntimeError):
@@ -111,6 +112,10 @@ _SIGS = {
     'ffcv_rrc_raw_workspace_bytes': (c_uint64, [c_int, c_int, c_int]),
     'ffcv_gather_samples': (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_void_p]),
     'ffcv_gather_raw_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_uint64]),
+    'ffcv_gather_rows': (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_int, c_uint64,
+                                 c_void_p, c_uint64, c_void_p]),
+    'ffcv_gather_rows_cutover': (c_uint64, []),
+    'ffcv_gather_rows_subwave': (c_uint64, []),
     'ffcv_jpeg_scan_stats': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'ffcv_jpeg_create': (c_int, [c_void_p, c_int, c_uint32, c_uint32, c_uint64]),
     'ffcv_jpeg_destroy': (c_int, [c_void_p]),
@@ -410,6 +415,35 @@ def rrc_raw_batch(base, samples, batch, crops, cutout_yx, flips, params: RRCPara
 def gather_raw_batch(base, samples, batch, out, out_stride, stream=None):
     _check(lib().ffcv_gather_raw_batch(_stream(stream), _p(base), _p(samples), int(batch),
                                        _p(out), int(out_stride)), 'ffcv_gather_raw_batch')
+
+
+def gather_rows_cutover():
+    """Row size in bytes from which ffcv_gather_rows runs its 2-D grid."""
+    return int(lib().ffcv_gather_rows_cutover())
+
+
+def gather_rows_subwave():
+    """Largest row size in bytes that ffcv_gather_rows gives 16 lanes (above: a wave)."""
+    return int(lib().ffcv_gather_rows_subwave())
+
+
+def gather_rows(base, base_bytes, row_off, ids, row_bytes, out, out_stride, status, stream=None, shape=None):
+    """``out[k * out_stride : + row_bytes] = base[row_off[ids[k]] : + row_bytes]``
+    in one launch (ffcv_gather_rows).  base: device uint8, 16-byte aligned,
+    allocated up to the next multiple of 16 past base_bytes; row_off: device
+    uint64 (or int64) per sample; ids: device int64 / uint64 [B]; status:
+    device int32[B] (0, or 8 with a zero-filled row for an id or a row out of
+    range).  ``shape``: diagnostics only, the dispatch shape (1: 16 lanes per
+    row, 2: a wave per row, 3: the 2-D grid)."""
+    args = (_stream(stream), _p(base), int(base_bytes), _p(row_off), int(row_off.shape[0]), _p(ids),
+            int(ids.shape[0]), int(row_bytes), _p(out), int(out_stride), _p(status))
+    if shape is None:
+        _check(lib().ffcv_gather_rows(*args), 'ffcv_gather_rows')
+        return
+    fn = lib().ffcv_gather_rows_shape   # not in ffcv_hip.h: bound on first use
+    fn.restype = c_int
+    fn.argtypes = _SIGS['ffcv_gather_rows'][1] + [c_int]
+    _check(fn(*args, int(shape)), 'ffcv_gather_rows_shape')
 
 
 def cutout_batch(images, yx, crop_size, fill, stream=None):

@@ -14,6 +14,9 @@ import numpy as np
 import torch as ch
 
 _cache = {}
+# zeroed bytes behind the file: kernels that read the resident bytes with
+# aligned wide loads may run this far past a sample's end
+PADDING = 64
 _lock = threading.Lock()
 
 
@@ -24,7 +27,7 @@ def upload_file(fname, device, chunk=256 << 20):
             return _cache[key]
         mm = np.memmap(fname, 'uint8', mode='r')
         n = mm.shape[0]
-        dev = ch.empty(n + 64, dtype=ch.uint8, device=device)
+        dev = ch.empty(n + PADDING, dtype=ch.uint8, device=device)
         dev[n:].zero_()
         pinned = ch.empty(min(chunk, n) or 1, dtype=ch.uint8).pin_memory()
         s = ch.cuda.Stream(device)

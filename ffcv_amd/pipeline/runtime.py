@@ -73,6 +73,24 @@ class DeviceDataset:
                                   int(sizes[jpg].max()) if jpg.any() else 1)
         return self._tables[f_ix]
 
+    @property
+    def data_bytes(self):
+        """Valid bytes of ``data`` (the file's size; the padding behind it excluded)."""
+        from ..memory_managers.device_cache import PADDING
+        return int(self.data.numel()) - PADDING
+
+    def row_offsets(self, f_ix):
+        """uint64[N] byte offsets into ``data`` of a pointer field's samples
+        (NDArrayField: metadata - data_base), built once and kept in HBM like
+        ``table()``; stored as the int64 of the same bits."""
+        if not hasattr(self, '_row_offsets'):
+            self._row_offsets = {}
+        if f_ix not in self._row_offsets:
+            ptr = np.ascontiguousarray(self.reader.metadata[f'f{f_ix}'], dtype=np.uint64)
+            off = ptr - np.uint64(self.data_base)
+            self._row_offsets[f_ix] = ch.from_numpy(off.view(np.int64)).to(self.device)
+        return self._row_offsets[f_ix]
+
     def arena_bytes(self, f_ix, max_batch):
         """JPEG scratch arena for launches of max_batch samples of field
         f_ix: the sum of the largest max_batch per-image bounds (one huge image
@@ -258,6 +276,30 @@ class BatchContext:
         buf[:B].view(-1).copy_(desc_host[:B * 32], non_blocking=True)
         self._staged_data = dev
         return buf[:B]
+
+    def stage_rows(self, f_ix, row_bytes, out):
+        """PCIe path of a fixed-size pointer field (NDArrayDecoder): gather
+        this batch's rows from the mmap (or the process cache's page slots)
+        into a pinned (capacity, row_bytes) buffer of this slot, then one
+        asynchronous copy of B * row_bytes into ``out`` on the slot stream.
+        The pinned buffer is guarded like ``_ids_host``: written only after
+        the copies of the slot's previous batch are done, and ``end_batch``
+        records the event that covers this batch's copy."""
+        from .. import libffcv as L
+        from ..memory_managers.process_cache import host_source
+        idx = np.asarray(self.batch_indices, dtype=np.int64)
+        B = len(idx)
+        key = ('rows', f_ix)
+        host = self._staging.get(key)
+        if host is None or host.numel() < self.batch_size * row_bytes:
+            host = self._staging[key] = ch.empty((self.batch_size, row_bytes), dtype=ch.uint8).pin_memory()
+        self._wait_host_buffers()
+        ptrs = self.dataset.reader.metadata[f'f{f_ix}'][idx].astype(np.uint64)
+        src, src_off = host_source(self.host_state, ptrs)
+        L.host_gather(src, src_off, np.full(B, row_bytes, np.uint64),
+                      np.arange(B, dtype=np.uint64) * np.uint64(row_bytes), host,
+                      nthreads=int(min(8, max(1, (B * row_bytes) >> 22))))
+        L.memcpy_h2d_async(out, host, B * row_bytes, self.stream)
 
     def any_mode(self, f_ix, mode):
         return self.dataset.has_mode(f_ix, mode)

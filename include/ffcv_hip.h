@@ -51,7 +51,8 @@ enum {
   FFCV_SAMPLE_CORRUPT = 4,         /* entropy stream inconsistent, or ends before its last block */
   FFCV_SAMPLE_GEOMETRY = 5,        /* SOF size != .beton metadata */
   FFCV_SAMPLE_RNG = 6,             /* > 623 MT19937 draws for one stream */
-  FFCV_SAMPLE_LABEL = 7            /* MixupToOneHot: label outside [0, num_classes) */
+  FFCV_SAMPLE_LABEL = 7,           /* MixupToOneHot: label outside [0, num_classes) */
+  FFCV_SAMPLE_RANGE = 8            /* ffcv_gather_rows: id outside the table, or row outside the bytes */
 };
 
 /* One sample of a batch, as resolved from the .beton metadata + allocation
@@ -252,6 +253,42 @@ int ffcv_gather_samples(void *stream, const ffcv_sample *table, uint64_t n_table
 int ffcv_gather_raw_batch(void *stream, const uint8_t *base,
                           const ffcv_sample *samples, int batch, uint8_t *out,
                           uint64_t out_stride);
+
+/* ndarray.py:19-45 NDArrayDecoder (one my_memcpy per sample) as ONE device
+ * gather of fixed-size rows out of the resident .beton bytes, the id -> offset
+ * lookup inside the kernel (no descriptor gather in front):
+ *
+ *   out[k * out_stride : + row_bytes] = base[row_off[ids[k]] : + row_bytes]
+ *
+ * bit for bit, for k in [0, batch).
+ *   base       : device bytes, 16-byte aligned; base_bytes of them are valid.
+ *                The ALLOCATION must extend to the next multiple of 16 past
+ *                base_bytes: rows may start at any byte offset and are read
+ *                with aligned dword loads, so the aligned dword that holds a
+ *                row's last byte is read whole (nothing further is: only
+ *                aligned 16-byte words holding at least one byte of a valid
+ *                row are touched).  The 64 bytes of padding behind the
+ *                HBM-resident file and the staging buffers satisfy this.
+ *   row_off    : device uint64[n_rows], byte offset of every sample's row
+ *   ids        : device uint64[batch] sample indices
+ *   out        : device bytes, any alignment; out_stride >= row_bytes, and
+ *                only the row_bytes bytes of each output row are written
+ *   status     : device int32[batch] out, required
+ * A row with ids[k] >= n_rows, or whose bytes do not lie inside
+ * [0, base_bytes) (checked without wrap-around), is not read: its output row
+ * is zero-filled and status[k] = FFCV_SAMPLE_RANGE; every other status[k] is
+ * FFCV_SAMPLE_OK.  Rows shorter than ffcv_gather_rows_cutover() bytes take a
+ * wave (up to ffcv_gather_rows_subwave() bytes: 16 lanes) each, several rows
+ * per workgroup; longer rows a 2-D grid of 16 KiB chunks by rows.
+ * batch == 0 returns FFCV_OK without a launch.  FFCV_EINVAL, before any
+ * launch, for a null pointer, batch < 0, row_bytes == 0, out_stride <
+ * row_bytes or a base that is not 16-byte aligned. */
+int ffcv_gather_rows(void *stream, const uint8_t *base, uint64_t base_bytes,
+                     const uint64_t *row_off, uint64_t n_rows,
+                     const uint64_t *ids, int batch, uint64_t row_bytes,
+                     uint8_t *out, uint64_t out_stride, int32_t *status);
+uint64_t ffcv_gather_rows_cutover(void);
+uint64_t ffcv_gather_rows_subwave(void);
 
 /* ------------------------------------------------------- JPEG decode -- */
 /* Baseline-sequential Huffman JPEG, 8-bit, 1 or 3 components, any 1x/2x
