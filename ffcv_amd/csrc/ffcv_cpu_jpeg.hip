@@ -7,7 +7,7 @@
 // tjDecompress2(TJPF_RGB, TJFLAG_FASTDCT): libjpeg-turbo's ifast IDCT
 // (jidctfst.c), fancy upsampling (jdsample.c) and the fixed-point YCbCr->RGB
 // tables (jdcolor.c).  This is that decode in plain C++ on the calling thread,
-// with the same arithmetic the gfx950 kernels use (ffcv_jpeg.hip), so a
+// with the same arithmetic the gfx950 kernels use (ffcv_jpeg.hip and its jpeg_*.h), so a
 // Loader on device='cpu' -- or on a machine without a GPU -- produces the
 // reference's pixels.  The device decoder stays the hot path; this file is
 // the CPU boundary only.
@@ -108,7 +108,7 @@ struct Dec {
 int rd16(const uint8_t *p) { return p[0] << 8 | p[1]; }
 
 // Marker walk up to the first SOS (jdmarker.c), with the acceptance rules of
-// the device parser (ffcv_jpeg.hip parse_header).  0 or a message.
+// the device parser (jpeg_entropy.h parse_header).  0 or a message.
 const char *parse(const uint8_t *b, size_t n, Dec &d) {
   if (n < 4 || b[0] != 0xFF || b[1] != 0xD8) return "not a JPEG (no SOI)";
   size_t p = 2;

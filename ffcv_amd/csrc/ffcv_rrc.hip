@@ -96,9 +96,6 @@ struct LdsSrc {
 // an area plan whose column records rrc_taps_kernel writes: both scales < 2
 // (scale_x = 1 / (dw / sw) < 2 exactly when sw < 2 dw)
 FFCV_HD bool area_walk_plan(const ResizePlan &P) { return P.kind == 2 && P.sw < 2 * P.dw && P.sh < 2 * P.dh; }
-#ifndef RRC_AREA_MAGIC
-#define RRC_AREA_MAGIC 1  // 0: the area walk rounds by v_rndne + v_cvt + v_med3 (A/B builds)
-#endif
 #ifndef RRC_WPE
 #define RRC_WPE 5  // waves per SIMD the raw kernel is compiled for (5 workgroups per CU by LDS)
 #endif
@@ -370,12 +367,12 @@ FFCV_DEV void rrc_band(const uint8_t *__restrict__ base, const ffcv_sample *__re
               cr = r;
             }
           }
-#if RRC_AREA_MAGIC
           // cvRound + saturate_cast<uchar>: the sums lie in [0, 255.5) (bytes
           // times weights that sum to 1 up to a few float roundings), so
           // S + 1.5 * 2^23 rounds S half-to-even into the float's low byte and
           // the saturation never acts: one (packed) add per value instead of
-          // v_rndne + v_cvt + v_med3, and the u8 bytes packed by v_perm
+          // v_rndne + v_cvt + v_med3, and the u8 bytes packed by v_perm (the
+          // v_rndne form was a build switch until commit 356ba29)
           uint32_t bz[12];
 #pragma unroll
           for (int i = 0; i < 12; i++) bz[i] = ffcv_f2u_bits(S[i] + 12582912.0f);
@@ -412,12 +409,6 @@ FFCV_DEV void rrc_band(const uint8_t *__restrict__ base, const ffcv_sample *__re
             w.z = wd[2];
             __builtin_nontemporal_store(w, (u32x3 *)((uint8_t *)o + px * 3));
           }
-#else
-          int v[12];
-#pragma unroll
-          for (int i = 0; i < 12; i++) v[i] = sat_u8i(ffcv_f2i_rn(S[i]));
-          put(dy, v);
-#endif
         }
         return;
       }

@@ -20,7 +20,7 @@ from ffcv_amd.synthetic import natural_image, encode_jpeg
 
 SOF0, SOF1, DHT, SOS, DQT, DRI, APP0, APP1, APP2, APP14, COM = \
     0xC0, 0xC1, 0xC4, 0xDA, 0xDB, 0xDD, 0xE0, 0xE1, 0xE2, 0xEE, 0xFE
-HDR_BYTES = 2048  # header bytes K1 stages in LDS (ffcv_jpeg.hip)
+HDR_BYTES = 2048  # header bytes K1 stages in LDS (jpeg_defs.h)
 
 Base = namedtuple('Base', 'name blob h w sub')          # sub: '4:2:0', '4:2:2', '4:4:4' or 'gray'
 Variant = namedtuple('Variant', 'name blob h w group')  # group: 'container', 'colour' or 'layout'

@@ -1,4 +1,4 @@
-"""The integer identities the linear walks (K2's fast path in ffcv_jpeg.hip,
+"""The integer identities the linear walks (K2's fast path in jpeg_color_resize.h,
 the raw kernel's walk in ffcv_rrc.hip) rest on, checked over their whole
 input ranges on the host.  Each replaces a step of OpenCV's
 HResizeLinear / VResizeLinearVec_32s8u (resize.cpp, the Q11 branch that
@@ -47,7 +47,7 @@ def test_vertical_pass_mulhi24():
 
 
 def test_lut_address_from_vertical_sum():
-    """lut_q<FP16> (ffcv_jpeg.hip): the channel-0 LUT entry of value
+    """lut_q<FP16> (jpeg_color_resize.h): the channel-0 LUT entry of value
     v = (x + 2) >> 2 sits at byte base + 2 v of the channel-major LDS table;
     the kernel computes it as ((x + 2 + 2 base) >> 1) & ~1 (base even), and a
     cutout fill f as base + 2 f."""

@@ -45,7 +45,7 @@ def _imdecode(L, blob, h, w):
 
 def test_surgery_round_trip(bases):
     assert ACCEPT_NAMES == J.ACCEPT and REJECT_NAMES == J.REJECT
-    src = open(os.path.join(ROOT, 'ffcv_amd', 'csrc', 'ffcv_jpeg.hip')).read()
+    src = open(os.path.join(ROOT, 'ffcv_amd', 'csrc', 'jpeg_defs.h')).read()
     assert int(re.search(r'^#define HDR_BYTES (\d+)', src, re.M).group(1)) == J.HDR_BYTES
     for b in bases:
         segs, scan = J.split(b.blob)

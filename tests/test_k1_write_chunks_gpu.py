@@ -37,7 +37,7 @@ def _torch():
 
 
 def _chunk():
-    src = open(os.path.join(ROOT, 'ffcv_amd', 'csrc', 'ffcv_jpeg.hip')).read()
+    src = open(os.path.join(ROOT, 'ffcv_amd', 'csrc', 'jpeg_defs.h')).read()
     return int(re.search(r'^#define K1_WCHUNK (\d+)', src, re.M).group(1))
 
 
