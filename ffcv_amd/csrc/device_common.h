@@ -159,8 +159,9 @@ FFCV_HD uint64_t splitmix64(uint64_t x) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-// Seeding contract: op ids 1 = crop, 2 = cutout, 3 = flip,
-// 4 = translate, 5 / 6 / 7 = brightness / contrast / saturation (color_common.h).
+// Seeding contract: op ids 1 = crop (decoder), 2 = cutout, 3 = flip,
+// 4 = translate, 5 / 6 / 7 = brightness / contrast / saturation (color_common.h),
+// 8 = crop transform (RandomResizedCrop, ffcv_rrc_images.hip).
 FFCV_HD uint32_t sample_seed(uint64_t loader_seed, uint64_t epoch, uint64_t sample, uint32_t op) {
   uint64_t h = splitmix64(loader_seed ^ ((uint64_t)op << 56));
   h = splitmix64(h ^ epoch);
@@ -168,8 +169,10 @@ FFCV_HD uint32_t sample_seed(uint64_t loader_seed, uint64_t epoch, uint64_t samp
   return (uint32_t)h;
 }
 
-// rgb_image.py:48-72 get_random_crop (Python round() = half-to-even = rint)
-FFCV_HD void random_crop(DevMT &m, uint32_t height, uint32_t width, const double *scale,
+// rgb_image.py:48-72 get_random_crop (Python round() = half-to-even = rint);
+// MT: DevMT, or a generator with its own mt_uniform (ffcv_rrc_images.hip)
+template <class MT>
+FFCV_HD void random_crop(MT &m, uint32_t height, uint32_t width, const double *scale,
                           const double *ratio, int32_t *out) {
   uint32_t area = height * width;
   double lr0 = log(ratio[0]), lr1 = log(ratio[1]);

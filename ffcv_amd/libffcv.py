@@ -146,6 +146,16 @@ _SIGS = {
     'ffcv_translate_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_void_p]),
     'ffcv_translate_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                      c_void_p]),
+    'ffcv_crop_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_uint64, c_uint64,
+                                     c_void_p, c_void_p]),
+    'ffcv_crop_draw_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_uint64, c_uint64,
+                                          c_void_p, c_void_p]),
+    'ffcv_rrc_images_batch': (c_int, [c_void_p, c_void_p, c_uint64, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
+    'ffcv_rrc_images_workspace_bytes': (c_uint64, [c_int, c_int, c_int, c_int, c_int]),
+    'ffcv_rrc_images_lds_bytes': (c_uint64, []),
+    'ffcv_rrc_images_batch_host': (c_int, [c_void_p, c_uint64, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                           c_void_p, c_uint64, c_void_p, c_int]),
     'ffcv_simple_aug_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
     'ffcv_color_jitter_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_double,
@@ -494,6 +504,84 @@ def translate_batch(inp, out, yx, padding, fill, stream=None):
     f = (ctypes.c_uint8 * 3)(*[int(x) for x in fill])
     _check(lib().ffcv_translate_batch(_stream(stream), _p(inp), _p(out), B, H, W, _p(yx), int(padding), f),
            'ffcv_translate_batch')
+
+
+def _ranges(scale, ratio):
+    return (c_double * 2)(float(scale[0]), float(scale[1])), (c_double * 2)(float(ratio[0]), float(ratio[1]))
+
+
+def crop_draw_batch(ids, height, width, scale, ratio, loader_seed, epoch, crops, status=None, stream=None):
+    """RandomResizedCrop (transform) windows (i, j, h, w) of the batch on the
+    device (op id 8): ids device int64 / uint64 [B], crops device int32 (B, 4)."""
+    sc, ra = _ranges(scale, ratio)
+    _check(lib().ffcv_crop_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]), int(height), int(width), sc, ra,
+                                      int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), _p(crops), _p(status)),
+           'ffcv_crop_draw_batch')
+
+
+def crop_draw_batch_host(ids, height, width, scale, ratio, loader_seed, epoch, status=None):
+    """The same draws on the host: int32 (B, 4) of (i, j, h, w)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    crops = np.empty((ids.size, 4), np.int32)
+    sc, ra = _ranges(scale, ratio)
+    _check(lib().ffcv_crop_draw_batch_host(_p(ids), int(ids.size), int(height), int(width), sc, ra,
+                                           int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), _p(crops), _p(status)),
+           'ffcv_crop_draw_batch_host')
+    return crops
+
+
+def rrc_images_lds_bytes():
+    """The largest staged source one workgroup of ffcv_rrc_images_batch keeps in LDS."""
+    return int(lib().ffcv_rrc_images_lds_bytes())
+
+
+def rrc_images_workspace_bytes(batch, height, width, out_h, out_w):
+    """Device bytes rrc_images_batch's workspace needs (0 in the LDS regime)."""
+    return int(lib().ffcv_rrc_images_workspace_bytes(int(batch), int(height), int(width), int(out_h), int(out_w)))
+
+
+def rrc_images_band_workspace_bytes(batch, out_h, out_w):
+    """The workspace of a band-regime launch (rrc_images_batch's ``regime=2``)."""
+    a256 = lambda x: (x + 255) & ~255  # noqa: E731
+    return a256(int(batch) * 32) + a256(int(batch) * 16) + rrc_raw_workspace_bytes(batch, out_h, out_w)
+
+
+def rrc_images_batch(inp, in_stride, batch, height, width, crops, cutout_yx, flips, params: RRCParams, out,
+                     status=None, workspace=None, stream=None, regime=None):
+    """Crop + INTER_AREA resize (+ flip / cutout / fp16 LUT through ``params``)
+    of a dense device uint8 batch of height x width x 3 images, image k at
+    ``inp + k * in_stride`` (ffcv_rrc_images_batch); ``workspace``: a device
+    uint8 tensor of rrc_images_workspace_bytes(), None where that is 0.
+    ``regime``: diagnostics only (1: the LDS kernel, 2: the band kernel with
+    a workspace of rrc_images_band_workspace_bytes())."""
+    wb = int(workspace.numel() * workspace.element_size()) if workspace is not None else 0
+    args = (_stream(stream), _p(inp), int(in_stride), int(batch), int(height), int(width), _p(crops), _p(cutout_yx),
+            _p(flips), ctypes.byref(params), _p(out), _p(status), _p(workspace), wb)
+    if regime is None:
+        _check(lib().ffcv_rrc_images_batch(*args), 'ffcv_rrc_images_batch')
+        return
+    fn = lib().ffcv_rrc_images_batch_regime   # not in ffcv_hip.h: bound on first use
+    fn.restype = c_int
+    fn.argtypes = _SIGS['ffcv_rrc_images_batch'][1] + [c_int]
+    _check(fn(*args, int(regime)), 'ffcv_rrc_images_batch_regime')
+
+
+def rrc_images_batch_host(inp: np.ndarray, crops, out: np.ndarray, status=None, nthreads=1):
+    """The resize on C-contiguous numpy uint8 arrays: inp (B, H, W, 3), crops
+    int32 (B, 4), out (B, out_h, out_w, 3); an invalid crop gives a zero image
+    and status 8 (status: int32 (B,) or None)."""
+    if not (isinstance(inp, np.ndarray) and isinstance(out, np.ndarray) and inp.dtype == np.uint8 and
+            out.dtype == np.uint8 and inp.ndim == 4 and out.ndim == 4 and inp.shape[3] == 3 and out.shape[3] == 3
+            and inp.flags.c_contiguous and out.flags.c_contiguous and out.shape[0] >= inp.shape[0]):
+        raise TypeError('rrc_images_batch_host: C-contiguous uint8 (B, H, W, 3) arrays are required')
+    crops = np.ascontiguousarray(crops, np.int32)
+    B, H, W = (int(x) for x in inp.shape[:3])
+    if crops.shape != (B, 4):
+        raise TypeError(f'rrc_images_batch_host: crops must be int32 ({B}, 4), got {crops.shape}')
+    _check(lib().ffcv_rrc_images_batch_host(_p(inp), H * W * 3, B, H, W, _p(crops), int(out.shape[1]),
+                                            int(out.shape[2]), _p(out), int(out[0].nbytes) if B else 0, _p(status),
+                                            int(max(1, nthreads))), 'ffcv_rrc_images_batch_host')
+    return out[:B]
 
 
 def simple_aug_batch(base, samples, batch, height, width, params: SimpleAugParams, flips, cutout_yx,

@@ -15,7 +15,9 @@ stages and generates stage functions with ``ast``.  Here:
    RandomTranslate (with RandomHorizontalFlip / Cutout in any order, then
    NormalizeImage(float16)) is lowered the same way into the small-image
    launch (``_lower_simple``).  A run of adjacent colour-jitter operations
-   becomes one launch of its own (``_lower_color``).
+   becomes one launch of its own (``_lower_color``).  A RandomResizedCrop
+   transform on device data absorbs the Cutout / RandomHorizontalFlip /
+   NormalizeImage(float16) behind it (``_lower_rrc_transform``).
 3. ``collect_requirements`` walks states exactly like graph.py:295-354.  A
    non-device-aware (user) operation that would receive device data gets an
    implicit device->host transfer in front of it, so reference-style numpy
@@ -150,8 +152,6 @@ class Graph:
     # ------------------------------------------------------------ fusion --
     def lower(self):
         from ..fields.rgb_image import ResizedCropRGBImageDecoder, SimpleRGBImageDecoder
-        from ..transforms import (Cutout, RandomHorizontalFlip, NormalizeImage, ToTensor, ToDevice,
-                                  ToTorchImage)
         if self.device.type != 'cuda':
             return
         for chain in self._chains.values():
@@ -163,39 +163,74 @@ class Graph:
             if not chain or not isinstance(chain[0], ResizedCropRGBImageDecoder):
                 continue
             dec = chain[0]
-            cutout = flip = norm = None
-            cut_before_flip = False
-            layout_changed = False
-            for op in chain[1:]:
-                if len(self.operation_to_node[op]) != 1:
-                    break
-                if isinstance(op, ToTensor):
-                    continue
-                if isinstance(op, ToTorchImage):
-                    layout_changed = True
-                    continue
-                if isinstance(op, ToDevice):
-                    t = ch.device(op.device)
-                    if t.type == 'cuda' and (t.index is None or t.index == (self.device.index or 0)):
-                        continue
-                    break
-                if isinstance(op, Cutout) and cutout is None and norm is None and not layout_changed:
-                    cutout = op
-                    cut_before_flip = flip is None
-                    op._absorbed = True
-                    continue
-                if isinstance(op, RandomHorizontalFlip) and flip is None and norm is None \
-                        and not layout_changed:
-                    flip = op
-                    op._absorbed = True
-                    continue
-                if isinstance(op, NormalizeImage) and norm is None and \
-                        np.dtype(op.original_dtype) == np.float16 and \
-                        np.asarray(op.lookup_table).shape == (256, 3):
-                    norm = op
-                    op._absorbed = True
-                break
+            cutout, flip, cut_before_flip, norm = self._scan_epilogue(chain[1:])
             dec.fuse(cutout=cutout, flip=flip, cutout_before_flip=cut_before_flip, normalize=norm)
+        for chain in self._chains.values():
+            self._lower_rrc_transform(chain)
+
+    def _scan_epilogue(self, ops):
+        """The operations a crop-and-resize launch can apply itself, scanned
+        through ToTensor, same-device ToDevice and ToTorchImage: Cutout and
+        RandomHorizontalFlip (each once, their order recorded, before any
+        layout change) and NormalizeImage(float16) with a (256, 3) table.
+        They are marked absorbed (they run as identities).  Returns (cutout,
+        flip, cutout_before_flip, normalize)."""
+        from ..transforms import (Cutout, RandomHorizontalFlip, NormalizeImage, ToTensor, ToDevice,
+                                  ToTorchImage)
+        cutout = flip = norm = None
+        cut_before_flip = False
+        layout_changed = False
+        for op in ops:
+            if len(self.operation_to_node[op]) != 1:
+                break
+            if isinstance(op, ToTensor):
+                continue
+            if isinstance(op, ToTorchImage):
+                layout_changed = True
+                continue
+            if isinstance(op, ToDevice):
+                t = ch.device(op.device)
+                if t.type == 'cuda' and (t.index is None or t.index == (self.device.index or 0)):
+                    continue
+                break
+            if getattr(op, '_absorbed', False):
+                break
+            if isinstance(op, Cutout) and cutout is None and norm is None and not layout_changed:
+                cutout = op
+                cut_before_flip = flip is None
+                op._absorbed = True
+                continue
+            if isinstance(op, RandomHorizontalFlip) and flip is None and norm is None \
+                    and not layout_changed:
+                flip = op
+                op._absorbed = True
+                continue
+            if isinstance(op, NormalizeImage) and norm is None and \
+                    np.dtype(op.original_dtype) == np.float16 and \
+                    np.asarray(op.lookup_table).shape == (256, 3):
+                norm = op
+                op._absorbed = True
+            break
+        return cutout, flip, cut_before_flip, norm
+
+    def _lower_rrc_transform(self, chain):
+        """A RandomResizedCrop transform whose input is on the device (an
+        RGB image decoder and device-aware operations in front of it) applies
+        the Cutout / RandomHorizontalFlip / NormalizeImage(float16) behind it
+        in its own launch (ffcv_rrc_images_batch), by the rules of the crop
+        decoders' lowering.  Runs after the decoder and colour lowerings:
+        operations they absorbed are left alone."""
+        from ..fields.rgb_image import SimpleRGBImageDecoder
+        from ..transforms import RandomResizedCrop
+        if not chain or not isinstance(chain[0], SimpleRGBImageDecoder):
+            return
+        for i, op in enumerate(chain):
+            if i == 0 or not isinstance(op, RandomResizedCrop) or len(self.operation_to_node[op]) != 1:
+                continue
+            if not all(getattr(o, 'device_aware', False) for o in chain[:i]):
+                continue
+            cutout, flip, cut_before_flip, norm = self._scan_epilogue(chain[i + 1:])
+            op.fuse(cutout=cutout, flip=flip, cutout_before_flip=cut_before_flip, normalize=norm)
 
     def _lower_simple(self, chain):
         """A plain SimpleRGBImageDecoder of raw samples followed (through

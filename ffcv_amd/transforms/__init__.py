@@ -1,6 +1,7 @@
 from .cutout import Cutout
 from .flip import RandomHorizontalFlip
 from .translate import RandomTranslate
+from .random_resized_crop import RandomResizedCrop
 from .color_jitter import RandomBrightness, RandomContrast, RandomSaturation
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .poison import Poison
@@ -11,6 +12,6 @@ from .module import ModuleWrapper
 from .common import Squeeze
 
 __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 'Squeeze', 'View',
-           'RandomHorizontalFlip', 'RandomTranslate', 'Cutout', 'ModuleWrapper',
+           'RandomResizedCrop', 'RandomHorizontalFlip', 'RandomTranslate', 'Cutout', 'ModuleWrapper',
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']

@@ -3,8 +3,10 @@
 Each stochastic operation ``op`` applied to dataset sample ``s`` in epoch
 ``e`` of a Loader seeded with ``seed`` owns a fresh MT19937 seeded with
 ``low32(splitmix64(splitmix64(splitmix64(seed ^ op<<56) ^ e) ^ s))``;
-op ids: 1 crop, 2 cutout, 3 flip, 4 translate, 5 brightness, 6 contrast,
-7 saturation.  The device kernels use the same function
+op ids: 1 crop (the crop decoders), 2 cutout, 3 flip, 4 translate,
+5 brightness, 6 contrast, 7 saturation, 8 crop transform (RandomResizedCrop:
+its own id, so that a pipeline with a crop decoder and the transform does not
+draw the same stream twice).  The device kernels use the same function
 (csrc/device_common.h sample_seed).  The reference itself draws from numba's
 per-thread generators seeded from OS entropy (nondeterministic); see
 DESIGN.md "RNG contract".

@@ -437,6 +437,77 @@ int ffcv_translate_batch(void *stream, const uint8_t *in, uint8_t *out,
                          int batch, int height, int width, const int32_t *yx,
                          int padding, const uint8_t fill[3]);
 
+/* ------------------------------------- RandomResizedCrop transform ---- */
+/* random_resized_crop.py: fast_crop.py get_random_crop on a batch of images
+ * of one common height x width, then cv::resize(INTER_AREA) of each window.
+ * Draws under the seeding contract with op id 8 ("crop transform"; id 1 is
+ * the crop DECODER's, so a pipeline with both draws two different streams),
+ * one lane per sample:
+ *   sample_ids : device uint64[B]
+ *   scale, ratio : host double[2] each (finite, scale >= 0, ratio > 0)
+ *   crops      : device int32[B][4] out (i, j, h, w)
+ *   status     : device int32[B] out (FFCV_SAMPLE_RNG when the sample's
+ *                MT19937 stream ran out), or NULL */
+int ffcv_crop_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                         int height, int width, const double scale[2],
+                         const double ratio[2], uint64_t loader_seed,
+                         uint64_t epoch, int32_t *crops, int32_t *status);
+/* The same draws on host arrays (the CPU-device Loader). */
+int ffcv_crop_draw_batch_host(const uint64_t *sample_ids, int batch,
+                              int height, int width, const double scale[2],
+                              const double ratio[2], uint64_t loader_seed,
+                              uint64_t epoch, int32_t *crops, int32_t *status);
+
+/* Image k of `out` = cv::resize(in_k[i:i+h, j:j+w], (out_h, out_w),
+ * INTER_AREA) with crops[k] = (i, j, h, w), then the epilogue of
+ * ffcv_rrc_raw_batch, bit for bit: flip where flips[k], cutout at
+ * cutout_yx[k] (p->cutout_size, p->cutout_fill, [3] = cutout before flip),
+ * the fp16 LUT when p->lut is set; p->out_stride bytes between output images
+ * (0 = dense), only each image's own bytes are written.
+ *   in    : device uint8, image k at in + k * in_stride, height x width x 3
+ *           with dense rows, at ANY byte alignment.  Rows are read with
+ *           aligned 16-byte loads: only aligned 16-byte words that hold at
+ *           least one byte of a crop row are touched, so the allocation must
+ *           extend to the 16-byte boundaries around
+ *           [in, in + batch * in_stride) (the rule of ffcv_gather_rows).
+ *   crops : device int32[B][4], validated on the device: with h <= 0, w <= 0,
+ *           i < 0, j < 0, i + h > height or j + w > width the image is not
+ *           read, its output is zero-filled and status[k] =
+ *           FFCV_SAMPLE_RANGE; every other status[k] is FFCV_SAMPLE_OK.
+ *   cutout_yx, flips, status : device, each may be NULL
+ *   out   : device, must not overlap `in`
+ * Two regimes, chosen from height and width: while the staged source
+ * (height rows of whole 16-byte chunks) is at most
+ * ffcv_rrc_images_lds_bytes(), ONE launch, a workgroup per image that stages
+ * the crop in LDS, builds its taps there and writes the final pixels (no
+ * workspace; an output so large that its out_h + out_w taps do not fit the
+ * workgroup's LDS beside the source takes the other regime).  Larger images
+ * run the band kernel of ffcv_rrc_raw_batch_ws behind a small descriptor
+ * kernel and need a 16-byte aligned workspace of
+ * ffcv_rrc_images_workspace_bytes() (0 in the LDS regime), overwritten by the
+ * launch.  batch == 0 returns FFCV_OK without a launch.  FFCV_EINVAL, before
+ * any launch, for a null in / crops / p / out, batch < 0, sizes <= 0,
+ * in_stride < height * width * 3, an out_stride smaller than an image, a
+ * cutout larger than the output, overlapping in and out, or a workspace
+ * that is too small or misaligned. */
+int ffcv_rrc_images_batch(void *stream, const uint8_t *in, uint64_t in_stride,
+                          int batch, int height, int width,
+                          const int32_t *crops, const int32_t *cutout_yx,
+                          const uint8_t *flips, const ffcv_rrc_params *p,
+                          void *out, int32_t *status, void *workspace,
+                          uint64_t workspace_bytes);
+uint64_t ffcv_rrc_images_workspace_bytes(int batch, int height, int width,
+                                         int out_h, int out_w);
+uint64_t ffcv_rrc_images_lds_bytes(void);
+/* The resize on host memory: resize() per image over nthreads threads, the
+ * same crop validation (status may be NULL), no epilogue (the host Cutout /
+ * flip / NormalizeImage are separate operations).  out_stride 0 = dense. */
+int ffcv_rrc_images_batch_host(const uint8_t *in, uint64_t in_stride,
+                               int batch, int height, int width,
+                               const int32_t *crops, int out_h, int out_w,
+                               uint8_t *out, uint64_t out_stride,
+                               int32_t *status, int nthreads);
+
 /* ------------------------------- fused small-image augmentation ------- */
 /* Geometric steps of ffcv_simple_aug_batch's program. */
 enum {
