@@ -47,6 +47,10 @@ FFCV_HD uint32_t cj_blend(double ratio, double omr, uint32_t v, double other) {
   return (uint32_t)(int32_t)z;
 }
 
+// RandomSolarization's table entry: v >= threshold ? 255 - v : v, the integer
+// threshold in [0, 256] carried as the step's float64 ratio
+FFCV_HD uint32_t cj_solarize(double threshold, uint32_t v) { return (double)v >= threshold ? 255u - v : v; }
+
 // color_jitter.py:86: l_img.mean() = float64(sum of the uint8 gray image) / float64(H * W);
 // the sum is an integer below 2^53, exact in any order
 FFCV_HD double cj_mean(uint64_t gray_sum, uint64_t pixels) { return (double)gray_sum / (double)pixels; }

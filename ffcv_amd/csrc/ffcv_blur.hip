@@ -1,0 +1,492 @@
+// ffcv_blur.hip -- GaussianBlur on a dense uint8 batch [B][H][W][3] (one
+// launch behind its draw launch), the draws of RandomGrayscale /
+// RandomSolarization / GaussianBlur (op ids 9-11), and the host twins.
+//
+// One kernel serves both regimes.  A 256-thread workgroup owns a tile of
+// output rows [y0, y1) x columns [x0, x1) of one image:
+//
+//   1. it stages the tile's source, rows [y0 - r, y1 + r) x columns
+//      [x0 - r, x1 + r) clipped to the image, as uint8 in LDS, with 16-byte
+//      aligned global loads whatever the byte offset (rows that span the
+//      image's width are one contiguous byte range and staged as one);
+//   2. horizontal pass: one float32 per staged row and tile column and
+//      channel into an LDS plane, border columns reflected at read time, a
+//      thread per four adjacent columns;
+//   3. vertical pass over that plane, border rows reflected at read time (a
+//      reflected row is always one of the staged rows), a thread per column
+//      and four adjacent rows, rounded to uint8 into the LDS bytes the source
+//      no longer needs;
+//   4. the bytes leave as 16-byte aligned stores at any alignment of dst;
+//      chunks cut by a row's (or the tile's) ends are stored byte by byte.
+//
+// The float32 intermediate never touches global memory.  An image whose
+// apply flag is 0 runs steps 1 and 4 only (a copy), on equal pieces of a
+// band's byte range instead of tiles.
+//
+//   whole image: 15 H W <= BLUR_LDS_BYTES -- one tile per image.  At the
+//     bound a workgroup takes 32.2 KiB of LDS, so four of them (16 waves, four
+//     per SIMD) share a CU's 160 KiB; a 32 x 32 image takes 15.2 KiB and the
+//     CU holds the eight workgroups (32 waves) that are its wave limit.
+//   bands: tiles of BLUR_BAND_ROWS rows; a band whose staged rows and float
+//     plane exceed BLUR_TILE_LDS at the image's width is split into column
+//     strips of the widest width that fits (blur_strip_cols).  A tile takes
+//     at most 40 KiB: four workgroups per CU again.
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "api_internal.h"
+#include "blur_common.h"
+
+#define BLUR_THREADS 256
+#define BLUR_LDS_BYTES 32768  // whole-image regime: 15 H W at most this
+#define BLUR_BAND_ROWS 32
+#define BLUR_TILE_LDS 40960  // dynamic LDS of one band-regime workgroup, at most
+#define BLUR_MAX_DIM 65535   // largest supported height and width
+// the weights in LDS: up to 31 and the +0 padding of a four-output walk (34 floats in all), in whole chunks
+#define BLUR_W_LDS 144
+
+__global__ void __launch_bounds__(64) uniform_draw_kernel(const uint64_t *__restrict__ ids, int B,
+                                                          uint64_t loader_seed, uint64_t epoch, uint32_t op_id,
+                                                          double p, double lo, double hi,
+                                                          uint8_t *__restrict__ apply, double *__restrict__ value,
+                                                          int32_t *__restrict__ status) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= B) return;
+  const int err = draw_color_jitter(k, ids[k], loader_seed, epoch, op_id, p, lo, hi, apply, value);
+  if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
+}
+
+__global__ void __launch_bounds__(64) blur_draw_kernel(const uint64_t *__restrict__ ids, int B,
+                                                       uint64_t loader_seed, uint64_t epoch, double p, double lo,
+                                                       double hi, int ksize, uint8_t *__restrict__ apply,
+                                                       double *__restrict__ sigma, float *__restrict__ weights,
+                                                       int32_t *__restrict__ status) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= B) return;
+  const int err = draw_blur(k, ids[k], loader_seed, epoch, p, lo, hi, ksize, apply, sigma, weights);
+  if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
+}
+
+// 16-byte chunks that can hold `bytes` contiguous bytes at any alignment
+FFCV_HD uint32_t blur_chunks(uint32_t bytes) { return (bytes + 30u) >> 4; }
+
+// How a launch cuts an image into tiles, and the LDS a workgroup takes.
+struct BlurPlan {
+  int band_rows, strip_cols, nbands, nstrips;
+  uint32_t u8_bytes;  // the uint8 region (staged source, later the output bytes), a multiple of 16
+  uint32_t lds;       // dynamic LDS: weights | uint8 region | float plane
+};
+
+// LDS of a tile of `rows` x `cols` outputs at radius r in an H x W image
+static void blur_tile_lds(int H, int W, int rows, int cols, int r, uint32_t *u8_bytes, uint32_t *lds) {
+  const uint32_t nrows = (uint32_t)std::min(H, rows + 2 * r), cw = (uint32_t)std::min(W, cols + 2 * r);
+  // one range when every tile spans the width, else a range per row (a tile
+  // at the image's edge may still span it and stage one range: never more
+  // chunks than its rows take apart, from two rows on; one row is the same
+  // either way).  A copy stages one range of at most rows x cols pixels:
+  // never more than this.
+  const uint32_t one = blur_chunks(nrows * 3u * cw) * 16u, apart = nrows * blur_chunks(3u * cw) * 16u;
+  const uint32_t staged = cols >= W ? one : std::max(one, apart);
+  *u8_bytes = staged + 32u;  // + the pixel reads' and the output chunks' look-ahead
+  *lds = BLUR_W_LDS + *u8_bytes + nrows * (uint32_t)cols * 12u;
+}
+
+static BlurPlan blur_plan(int H, int W, int ksize) {
+  const int r = (ksize - 1) / 2;
+  BlurPlan P;
+  if ((uint64_t)H * W * 15u <= BLUR_LDS_BYTES) {
+    P.band_rows = H;
+    P.strip_cols = W;
+  } else {
+    P.band_rows = std::min(H, BLUR_BAND_ROWS);
+    uint32_t u8, lds;
+    blur_tile_lds(H, W, P.band_rows, W, r, &u8, &lds);
+    P.strip_cols = W;
+    if (lds > BLUR_TILE_LDS) {
+      // per strip column: 15 bytes per staged row; fixed: the halo columns, a row's chunk slack, the weights
+      const int nrows = std::min(H, P.band_rows + 2 * r);
+      int c = (BLUR_TILE_LDS - 176 - nrows * (6 * r + 32)) / (15 * nrows);
+      for (c = std::max(1, std::min(c, W));; c--) {
+        blur_tile_lds(H, W, P.band_rows, c, r, &u8, &lds);
+        if (lds <= BLUR_TILE_LDS || c == 1) break;
+      }
+      P.strip_cols = c;
+    }
+  }
+  P.nbands = (H + P.band_rows - 1) / P.band_rows;
+  P.nstrips = (W + P.strip_cols - 1) / P.strip_cols;
+  blur_tile_lds(H, W, P.band_rows, P.strip_cols, r, &P.u8_bytes, &P.lds);
+  return P;
+}
+
+__global__ void __launch_bounds__(BLUR_THREADS)
+    gaussian_blur_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint64_t dst_stride, int H, int W,
+                         int ksize, const uint8_t *__restrict__ apply, const float *__restrict__ weights,
+                         BlurPlan P) {
+  extern __shared__ uint4 blur_smem[];
+  typedef uint32_t bx4_t __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(1))) bx4_t gx4_t;
+  float *s_w = (float *)blur_smem;
+  bx4_t *s_u8 = (bx4_t *)((uint8_t *)blur_smem + BLUR_W_LDS);
+  float *s_h = (float *)((uint8_t *)blur_smem + BLUR_W_LDS + P.u8_bytes);
+  const int t = threadIdx.x;
+  const uint32_t per = (uint32_t)P.nbands * P.nstrips;
+  const uint32_t k = blockIdx.x / per, rem = blockIdx.x - k * per;
+  const int band = rem / P.nstrips, strip = rem - band * P.nstrips;
+
+  // the image's decision (the same for the whole workgroup)
+  const bool on = apply[k] != 0;
+  const int r = (ksize - 1) / 2;
+  const int y0 = band * P.band_rows, y1 = min(H, y0 + P.band_rows);
+  const int x0 = strip * P.strip_cols, x1 = min(W, x0 + P.strip_cols);
+  const int lo = max(0, y0 - r), hi = min(H, y1 + r), cl = max(0, x0 - r), ch = min(W, x1 + r);
+  const int nrows = hi - lo, cw = ch - cl, rows = y1 - y0, tc = x1 - x0;
+
+  // ---- stage source rows [lo, hi) x columns [cl, ch): one contiguous byte
+  // range when they span the width, else a range per row in whole chunks;
+  // 16-byte aligned loads (an aligned chunk holding a byte of a range never
+  // crosses a page).  A copy needs no halo and no columns: the band's rows
+  // are one byte range of the image, and the band's workgroups (one per
+  // strip) take an equal piece of it each, never more than a tile's bytes.
+  const uint64_t step = (uint64_t)W * 3u;
+  const uint32_t band_bytes = (uint32_t)rows * 3u * W, piece = (band_bytes + P.nstrips - 1) / P.nstrips;
+  const uint32_t cp0 = min(band_bytes, (uint32_t)strip * piece), cp_len = min(piece, band_bytes - cp0);
+  if (!on && cp_len == 0) return;
+  const uint64_t src0 = (uint64_t)(uintptr_t)src + (uint64_t)k * H * step +
+                        (on ? ((uint64_t)lo * W + cl) * 3u : (uint64_t)y0 * step + cp0);
+  const bool span = !on || cw == W;
+  const int n_srows = span ? 1 : nrows;
+  const uint32_t srow_bytes = !on ? cp_len : (span ? (uint32_t)nrows * 3u * W : 3u * cw);
+  const int nchr = (int)blur_chunks(srow_bytes);
+  const int pitch = span ? 3 * W : nchr * 16;  // LDS bytes from a staged row to the next
+  const int lead0 = (int)(src0 & 15), stepmod = span ? 0 : (int)(step & 15);
+  for (int i = t; i < n_srows * nchr; i += BLUR_THREADS) {
+    const int rr = i / nchr, c = i - rr * nchr;
+    const uint64_t ra = src0 + (uint64_t)rr * step;
+    if (c < (int)(((ra & 15) + srow_bytes + 15) >> 4)) s_u8[i] = ((gx4_t *)(uintptr_t)(ra & ~(uint64_t)15))[c];
+  }
+  if (t < BLUR_W_LDS / 4) s_w[t] = on && t < ksize ? weights[(uint64_t)k * FFCV_BLUR_WROW + t] : 0.f;  // padded with +0
+  __syncthreads();
+  const uint8_t *s_bytes = (const uint8_t *)s_u8;
+  // first byte of staged row `row` (column cl)
+  auto rowoff = [&](int row) -> int { return row * pitch + ((lead0 + row * stepmod) & 15); };
+  // a pixel's R | G << 8 | B << 16 from two ALIGNED 4-byte LDS reads joined by
+  // v_alignbyte (misaligned LDS reads are several times slower); reads up to
+  // 7 bytes past the pixel's first, inside the region's look-ahead
+  auto pixel = [&](const uint8_t *a) -> uint32_t {
+    const uint32_t *qa = (const uint32_t *)__builtin_align_down(a, 4);
+    return __builtin_amdgcn_alignbyte(qa[1], qa[0], (uint32_t)(a - (const uint8_t *)qa));
+  };
+
+  const int pitchf = 3 * tc;  // floats per row of the plane
+  uint8_t *s_out = (uint8_t *)s_u8;
+  if (on) {
+    // Both passes give a thread four adjacent outputs along the pass's axis
+    // and walk the k + 3 source values under them once: each value is read
+    // and converted once and meets the four outputs' weights (w_m, w_m-1,
+    // w_m-2, w_m-3, kept in registers as the walk moves on).  Every output
+    // still adds its taps in ascending order.  Taps outside 0 .. k - 1 have
+    // weight +0 (s_w is padded): their products are zeros, which leave a sum
+    // as it is, and an accumulator that starts at +0 takes its first product
+    // exactly.
+    // ---- horizontal pass: a thread per staged row and four tile columns
+    const int ngx = (tc + 3) >> 2;
+    for (int i = t; i < nrows * ngx; i += BLUR_THREADS) {
+      const int row = i / ngx, xg = 4 * (i - row * ngx);
+      const int last = ksize + min(4, tc - xg) - 2;  // the walk's last step: no column past the tile's halo
+      const uint8_t *base = s_bytes + rowoff(row) - 3 * cl;
+      const int xs = x0 + xg - r;
+      float a[12];
+#pragma unroll
+      for (int e = 0; e < 12; e++) a[e] = 0.f;
+      float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3;
+      for (int m = 0; m <= last; m++) {
+        w3 = w2;
+        w2 = w1;
+        w1 = w0;
+        w0 = s_w[m];
+        const uint32_t v = pixel(base + 3 * blur_reflect(xs + m, W));
+        const float f[3] = {(float)(v & 0xffu), (float)((v >> 8) & 0xffu), (float)((v >> 16) & 0xffu)};
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          a[c] = blur_add(a[c], blur_mul(w0, f[c]));
+          a[3 + c] = blur_add(a[3 + c], blur_mul(w1, f[c]));
+          a[6 + c] = blur_add(a[6 + c], blur_mul(w2, f[c]));
+          a[9 + c] = blur_add(a[9 + c], blur_mul(w3, f[c]));
+        }
+      }
+      float *o = s_h + row * pitchf + 3 * xg;
+#pragma unroll
+      for (int e = 0; e < 12; e++)
+        if (e < 3 * (tc - xg)) o[e] = a[e];
+    }
+    __syncthreads();
+    // ---- vertical pass: a thread per float column and four output rows;
+    // the rounded bytes go, dense, where the staged source was
+    const int ngy = (rows + 3) >> 2;
+    for (int i = t; i < ngy * pitchf; i += BLUR_THREADS) {
+      const int g = i / pitchf, c = i - g * pitchf, yg = 4 * g;
+      const int nv = min(4, rows - yg);
+      const float *col = s_h + c - lo * pitchf;
+      const int ys = y0 + yg - r;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f, w3;
+      for (int m = 0; m <= ksize + nv - 2; m++) {  // no row past the tile's halo
+        w3 = w2;
+        w2 = w1;
+        w1 = w0;
+        w0 = s_w[m];
+        const float h = col[blur_reflect(ys + m, H) * pitchf];
+        a0 = blur_add(a0, blur_mul(w0, h));
+        a1 = blur_add(a1, blur_mul(w1, h));
+        a2 = blur_add(a2, blur_mul(w2, h));
+        a3 = blur_add(a3, blur_mul(w3, h));
+      }
+      uint8_t *o = s_out + yg * pitchf + c;
+      o[0] = (uint8_t)blur_round_u8(a0);
+      if (nv > 1) o[pitchf] = (uint8_t)blur_round_u8(a1);
+      if (nv > 2) o[2 * pitchf] = (uint8_t)blur_round_u8(a2);
+      if (nv > 3) o[3 * pitchf] = (uint8_t)blur_round_u8(a3);
+    }
+    __syncthreads();
+  }
+
+  // ---- write back: the bytes are in LDS, the tile's, dense (blurred), or
+  // the copy's piece as staged.  Rows that span the width leave as one byte
+  // range.  Whole 16-byte chunks of dst inside a range are one store,
+  // assembled from five aligned LDS dwords; the chunks cut by its ends go
+  // byte by byte.
+  const bool ospan = !on || tc == W;
+  const int n_orows = ospan ? 1 : rows;
+  const uint32_t orow_bytes = !on ? cp_len : (ospan ? band_bytes : 3u * tc);
+  const int onch = (int)blur_chunks(orow_bytes);
+  const uint64_t dst0 = (uint64_t)(uintptr_t)dst + (uint64_t)k * dst_stride +
+                        (on ? ((uint64_t)y0 * W + x0) * 3u : (uint64_t)y0 * step + cp0);
+  for (int i = t; i < n_orows * onch; i += BLUR_THREADS) {
+    const int y = i / onch, c = i - y * onch;
+    const uint64_t da = dst0 + (uint64_t)y * step;
+    const int dl = (int)(da & 15), c0 = 16 * c;  // the range is bytes [dl, dl + orow_bytes) of the aligned row
+    if (c0 >= dl + (int)orow_bytes) continue;
+    const uint8_t *sp = s_bytes + (on ? y * pitchf : lead0) + (c0 - dl);
+    uint8_t *gb = (uint8_t *)(uintptr_t)(da & ~(uint64_t)15) + c0;
+    if (c0 >= dl && c0 + 16 <= dl + (int)orow_bytes) {
+      const uint32_t *q = (const uint32_t *)__builtin_align_down(sp, 4);
+      const uint32_t sh = (uint32_t)(sp - (const uint8_t *)q);
+      const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
+      bx4_t o;
+      o.x = __builtin_amdgcn_alignbyte(q1, q0, sh);
+      o.y = __builtin_amdgcn_alignbyte(q2, q1, sh);
+      o.z = __builtin_amdgcn_alignbyte(q3, q2, sh);
+      o.w = __builtin_amdgcn_alignbyte(q4, q3, sh);
+      *(gx4_t *)gb = o;
+    } else {
+      for (int j = 0; j < 16; j++) {
+        const int b = c0 + j - dl;
+        if (b >= 0 && b < (int)orow_bytes) gb[j] = sp[j];
+      }
+    }
+  }
+}
+
+namespace {
+
+bool uniform_args_ok(const char *who, const void *ids, int batch, int op_id, double p, double lo, double hi,
+                     const void *apply, const void *value) {
+  if (batch < 0 || !ids || !apply || !value || op_id < 9 || op_id > 11 || !(p >= 0.0 && p <= 1.0) ||
+      !std::isfinite(lo) || !std::isfinite(hi) || !(lo <= hi)) {
+    ffcv::set_error("%s: invalid arguments (op_id %d, p %g, range %g .. %g)", who, op_id, p, lo, hi);
+    return false;
+  }
+  return true;
+}
+
+bool blur_draw_args_ok(const char *who, const void *ids, int batch, double p, double lo, double hi, int ksize,
+                       const void *apply, const void *sigma, const void *weights) {
+  if (batch < 0 || !ids || !apply || !sigma || !weights || !(p >= 0.0 && p <= 1.0) || !std::isfinite(lo) ||
+      !std::isfinite(hi) || !(lo > 0.0) || !(lo <= hi) || ksize < 1 || ksize > FFCV_BLUR_MAX_K || !(ksize & 1)) {
+    ffcv::set_error("%s: invalid arguments (p %g, sigma %g .. %g, ksize %d)", who, p, lo, hi, ksize);
+    return false;
+  }
+  return true;
+}
+
+// the checks of both pixel entries; *stride: the resolved dst stride
+bool blur_args_ok(const char *who, const uint8_t *src, const uint8_t *dst, int batch, int height, int width,
+                  int ksize, const void *apply, const void *weights, uint64_t dst_stride, uint64_t *stride) {
+  if (!src || !dst || !apply || !weights || batch < 0 || height <= 0 || width <= 0) {
+    ffcv::set_error("%s: invalid arguments", who);
+    return false;
+  }
+  if (height > BLUR_MAX_DIM || width > BLUR_MAX_DIM) {
+    ffcv::set_error("%s: images of %dx%d exceed the supported %d", who, height, width, BLUR_MAX_DIM);
+    return false;
+  }
+  if (ksize < 1 || ksize > FFCV_BLUR_MAX_K || !(ksize & 1) || (ksize - 1) / 2 >= std::min(height, width)) {
+    ffcv::set_error("%s: ksize %d on %dx%d images (odd, 1 .. %d, (ksize - 1) / 2 < min(height, width))", who, ksize,
+                    height, width, FFCV_BLUR_MAX_K);
+    return false;
+  }
+  const uint64_t img = (uint64_t)height * width * 3;
+  *stride = dst_stride ? dst_stride : img;
+  if (*stride < img) {
+    ffcv::set_error("%s: dst_stride %llu for images of %llu bytes", who, (unsigned long long)dst_stride,
+                    (unsigned long long)img);
+    return false;
+  }
+  if (batch > 0) {
+    const uintptr_t a0 = (uintptr_t)src, a1 = a0 + (uint64_t)batch * img;
+    const uintptr_t b0 = (uintptr_t)dst, b1 = b0 + (uint64_t)(batch - 1) * *stride + img;
+    if (a0 < b1 && b0 < a1) {
+      ffcv::set_error("%s: src and dst overlap (the blur is out of place)", who);
+      return false;
+    }
+  }
+  return true;
+}
+
+// One image on the host: the kernel's arithmetic in the kernel's order.
+void blur_image_host(const uint8_t *in, uint8_t *out, int H, int W, int ksize, const float *w,
+                     std::vector<float> &plane) {
+  const int r = (ksize - 1) / 2, pitchf = 3 * W;
+  plane.resize((size_t)H * pitchf);
+  for (int y = 0; y < H; y++)
+    for (int x = 0; x < W; x++)
+      for (int c = 0; c < 3; c++) {
+        const uint8_t *row = in + (size_t)y * pitchf + c;
+        float acc = blur_mul(w[0], (float)row[3 * blur_reflect(x - r, W)]);
+        for (int j = 1; j < ksize; j++) acc = blur_add(acc, blur_mul(w[j], (float)row[3 * blur_reflect(x - r + j, W)]));
+        plane[(size_t)y * pitchf + 3 * x + c] = acc;
+      }
+  for (int y = 0; y < H; y++)
+    for (int c = 0; c < pitchf; c++) {
+      const float *col = plane.data() + c;
+      float acc = blur_mul(w[0], col[(size_t)blur_reflect(y - r, H) * pitchf]);
+      for (int j = 1; j < ksize; j++)
+        acc = blur_add(acc, blur_mul(w[j], col[(size_t)blur_reflect(y - r + j, H) * pitchf]));
+      out[(size_t)y * pitchf + c] = (uint8_t)blur_round_u8(acc);
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------- C ABI -------
+extern "C" {
+
+int ffcv_uniform_draw_batch(void *stream, const uint64_t *sample_ids, int batch, uint64_t loader_seed,
+                            uint64_t epoch, int op_id, double p, double lo, double hi, uint8_t *apply,
+                            double *value, int32_t *status) {
+  if (!uniform_args_ok("ffcv_uniform_draw_batch", sample_ids, batch, op_id, p, lo, hi, apply, value))
+    return FFCV_EINVAL;
+  if (batch == 0) return FFCV_OK;
+  hipLaunchKernelGGL(uniform_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream), sample_ids,
+                     batch, loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, value, status);
+  FFCV_LAUNCH_CHECK("uniform_draw_kernel");
+  return FFCV_OK;
+}
+
+int ffcv_uniform_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch,
+                                 int op_id, double p, double lo, double hi, uint8_t *apply, double *value) {
+  if (!uniform_args_ok("ffcv_uniform_draw_batch_host", sample_ids, batch, op_id, p, lo, hi, apply, value))
+    return FFCV_EINVAL;
+  int err = 0;
+  for (int k = 0; k < batch; k++)
+    err |= draw_color_jitter(k, sample_ids[k], loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, value);
+  if (err) {
+    ffcv::set_error("ffcv_uniform_draw_batch_host: MT19937 stream exhausted");
+    return FFCV_EINVAL;
+  }
+  return FFCV_OK;
+}
+
+int ffcv_blur_draw_batch(void *stream, const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch,
+                         double p, double sigma_lo, double sigma_hi, int ksize, uint8_t *apply, double *sigma,
+                         float *weights, int32_t *status) {
+  if (!blur_draw_args_ok("ffcv_blur_draw_batch", sample_ids, batch, p, sigma_lo, sigma_hi, ksize, apply, sigma,
+                         weights))
+    return FFCV_EINVAL;
+  if (batch == 0) return FFCV_OK;
+  hipLaunchKernelGGL(blur_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream), sample_ids,
+                     batch, loader_seed, epoch, p, sigma_lo, sigma_hi, ksize, apply, sigma, weights, status);
+  FFCV_LAUNCH_CHECK("blur_draw_kernel");
+  return FFCV_OK;
+}
+
+int ffcv_blur_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch, double p,
+                              double sigma_lo, double sigma_hi, int ksize, uint8_t *apply, double *sigma,
+                              float *weights) {
+  if (!blur_draw_args_ok("ffcv_blur_draw_batch_host", sample_ids, batch, p, sigma_lo, sigma_hi, ksize, apply, sigma,
+                         weights))
+    return FFCV_EINVAL;
+  int err = 0;
+  for (int k = 0; k < batch; k++)
+    err |= draw_blur(k, sample_ids[k], loader_seed, epoch, p, sigma_lo, sigma_hi, ksize, apply, sigma, weights);
+  if (err) {
+    ffcv::set_error("ffcv_blur_draw_batch_host: MT19937 stream exhausted");
+    return FFCV_EINVAL;
+  }
+  return FFCV_OK;
+}
+
+uint64_t ffcv_gaussian_blur_lds_bytes(void) { return BLUR_LDS_BYTES; }
+uint64_t ffcv_gaussian_blur_band_rows(void) { return BLUR_BAND_ROWS; }
+
+uint64_t ffcv_gaussian_blur_strip_cols(int height, int width, int ksize) {
+  if (height <= 0 || width <= 0 || height > BLUR_MAX_DIM || width > BLUR_MAX_DIM || ksize < 1 ||
+      ksize > FFCV_BLUR_MAX_K || !(ksize & 1))
+    return 0;
+  return (uint64_t)blur_plan(height, width, ksize).strip_cols;
+}
+
+int ffcv_gaussian_blur_batch(void *stream, const uint8_t *src, uint8_t *dst, int batch, int height, int width,
+                             int ksize, const uint8_t *apply, const float *weights, uint64_t dst_stride_bytes) {
+  uint64_t stride;
+  if (!blur_args_ok("ffcv_gaussian_blur_batch", src, dst, batch, height, width, ksize, apply, weights,
+                    dst_stride_bytes, &stride))
+    return FFCV_EINVAL;
+  if (batch == 0) return FFCV_OK;
+  const BlurPlan P = blur_plan(height, width, ksize);
+  const uint64_t blocks = (uint64_t)batch * P.nbands * P.nstrips;
+  if (blocks > 0x7fffffffull) {
+    ffcv::set_error("ffcv_gaussian_blur_batch: %llu workgroups exceed one launch", (unsigned long long)blocks);
+    return FFCV_EINVAL;
+  }
+  hipLaunchKernelGGL(gaussian_blur_kernel, dim3((unsigned)blocks), dim3(BLUR_THREADS), (size_t)P.lds,
+                     ffcv::as_stream(stream), src, dst, stride, height, width, ksize, apply, weights, P);
+  FFCV_LAUNCH_CHECK("gaussian_blur_kernel");
+  return FFCV_OK;
+}
+
+int ffcv_gaussian_blur_batch_host(const uint8_t *src, uint8_t *dst, int batch, int height, int width, int ksize,
+                                  const uint8_t *apply, const float *weights, uint64_t dst_stride_bytes,
+                                  int nthreads) {
+  uint64_t stride;
+  if (!blur_args_ok("ffcv_gaussian_blur_batch_host", src, dst, batch, height, width, ksize, apply, weights,
+                    dst_stride_bytes, &stride))
+    return FFCV_EINVAL;
+  if (batch == 0) return FFCV_OK;
+  const uint64_t img = (uint64_t)height * width * 3;
+  std::atomic<int> next{0};
+  auto work = [&]() {
+    std::vector<float> plane;
+    for (int k = next.fetch_add(1); k < batch; k = next.fetch_add(1)) {
+      const uint8_t *in = src + (uint64_t)k * img;
+      uint8_t *out = dst + (uint64_t)k * stride;
+      if (apply[k])
+        blur_image_host(in, out, height, width, ksize, weights + (uint64_t)k * FFCV_BLUR_WROW, plane);
+      else
+        std::memcpy(out, in, img);
+    }
+  };
+  const int T = std::max(1, std::min(nthreads, batch));
+  std::vector<std::thread> th;
+  th.reserve(T - 1);
+  for (int t = 1; t < T; t++) th.emplace_back(work);
+  work();
+  for (auto &x : th) x.join();
+  return FFCV_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,7 @@
 // ffcv_color.hip -- RandomBrightness / RandomContrast / RandomSaturation
-// (color_jitter.py) as one-launch device colour jitter, with the host twin.
+// (color_jitter.py) as one-launch device colour jitter, with the host twin;
+// RandomGrayscale and RandomSolarization are two more steps
+// of the same launch.
 //
 // One kernel serves both regimes.  A workgroup stages a run of whole pixels
 // of one image in LDS (the whole image when it fits CJ_LDS_BYTES, else a tile
@@ -103,9 +105,10 @@ __global__ void __launch_bounds__(CJ_THREADS)
   for (int i = s0; i < s1; i++) {
     if (!apply[(uint64_t)i * B + k]) continue;
     const uint32_t st = (prog >> (8 * i)) & 0xffu;
-    const double r = ratio[(uint64_t)i * B + k];
+    // grayscale is saturation at ratio 0 (0 v + 1 gray is exact)
+    const double r = st == FFCV_CJ_GRAYSCALE ? 0.0 : ratio[(uint64_t)i * B + k];
     const double omr = cj_one_minus(r);
-    if (st == FFCV_CJ_SATURATION) {
+    if (st == FFCV_CJ_SATURATION || st == FFCV_CJ_GRAYSCALE) {
       for (uint32_t q = t; q < npix; q += CJ_THREADS) {
         const uint32_t v = pixel(q);
         const uint32_t c0 = v & 0xffu, c1 = (v >> 8) & 0xffu, c2 = v >> 16;
@@ -118,13 +121,14 @@ __global__ void __launch_bounds__(CJ_THREADS)
       __syncthreads();
       continue;
     }
-    // brightness / contrast: a 256-entry table of the image, then a byte map
+    // brightness / contrast / solarize: a 256-entry table of the image, then a byte map
     double other = 0.0;
     if (st == FFCV_CJ_CONTRAST) {
       const uint64_t total = mode == CJ_WHOLE ? (uint64_t)gray_sum() : (uint64_t)ws[k];
       other = cj_mean(total, npx);
     }
-    s_tab[t] = (uint8_t)cj_blend(r, omr, (uint32_t)t, other);  // CJ_THREADS == 256
+    s_tab[t] = (uint8_t)(st == FFCV_CJ_SOLARIZE ? cj_solarize(r, (uint32_t)t)
+                                                : cj_blend(r, omr, (uint32_t)t, other));  // CJ_THREADS == 256
     __syncthreads();
     // whole words covering the staged bytes (the bytes around them are not written back)
     const uint32_t w1 = (lead + nbytes + 3) >> 2;
@@ -166,7 +170,7 @@ static int cj_check_program(const char *who, const ffcv_color_jitter_params *p, 
   *contrast_at = -1;
   for (int i = 0; i < p->n_steps; i++) {
     const int st = p->steps[i];
-    if (st != FFCV_CJ_BRIGHTNESS && st != FFCV_CJ_CONTRAST && st != FFCV_CJ_SATURATION) {
+    if (st < FFCV_CJ_BRIGHTNESS || st > FFCV_CJ_SOLARIZE) {
       ffcv::set_error("%s: unknown step %d at position %d", who, st, i);
       return FFCV_EINVAL;
     }
@@ -295,9 +299,9 @@ int ffcv_color_jitter_batch_host(uint8_t *images, int batch, int height, int wid
     for (int i = 0; i < params->n_steps; i++) {
       if (!apply[(uint64_t)i * batch + k]) continue;
       const int st = params->steps[i];
-      const double r = ratio[(uint64_t)i * batch + k];
+      const double r = st == FFCV_CJ_GRAYSCALE ? 0.0 : ratio[(uint64_t)i * batch + k];
       const double omr = cj_one_minus(r);
-      if (st == FFCV_CJ_SATURATION) {
+      if (st == FFCV_CJ_SATURATION || st == FFCV_CJ_GRAYSCALE) {
         for (uint64_t q = 0; q < npx; q++) {
           uint8_t *o = im + 3 * q;
           const uint32_t c0 = o[0], c1 = o[1], c2 = o[2];
@@ -315,7 +319,8 @@ int ffcv_color_jitter_batch_host(uint8_t *images, int batch, int height, int wid
         other = cj_mean(total, npx);
       }
       uint8_t tab[256];
-      for (uint32_t v = 0; v < 256; v++) tab[v] = (uint8_t)cj_blend(r, omr, v, other);
+      for (uint32_t v = 0; v < 256; v++)
+        tab[v] = (uint8_t)(st == FFCV_CJ_SOLARIZE ? cj_solarize(r, v) : cj_blend(r, omr, v, other));
       for (uint64_t j = 0; j < npx * 3; j++) im[j] = tab[im[j]];
     }
   }

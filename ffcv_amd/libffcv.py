@@ -167,6 +167,21 @@ _SIGS = {
     'ffcv_color_jitter_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_uint64]),
     'ffcv_color_jitter_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'ffcv_uniform_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_double, c_double,
+                                        c_double, c_void_p, c_void_p, c_void_p]),
+    'ffcv_uniform_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_double, c_double, c_double,
+                                             c_void_p, c_void_p]),
+    'ffcv_blur_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_double,
+                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ffcv_blur_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_double, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
+    'ffcv_gaussian_blur_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                         c_void_p, c_uint64]),
+    'ffcv_gaussian_blur_batch_host': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                              c_uint64, c_int]),
+    'ffcv_gaussian_blur_lds_bytes': (c_uint64, []),
+    'ffcv_gaussian_blur_band_rows': (c_uint64, []),
+    'ffcv_gaussian_blur_strip_cols': (c_uint64, [c_int, c_int, c_int]),
     'ffcv_mixup_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int]),
     'ffcv_mixup_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int,
                                       c_int]),
@@ -594,7 +609,7 @@ def simple_aug_batch(base, samples, batch, height, width, params: SimpleAugParam
            'ffcv_simple_aug_batch')
 
 
-CJ_BRIGHTNESS, CJ_CONTRAST, CJ_SATURATION = 1, 2, 3
+CJ_BRIGHTNESS, CJ_CONTRAST, CJ_SATURATION, CJ_GRAYSCALE, CJ_SOLARIZE = 1, 2, 3, 4, 5
 
 
 def color_jitter_params(steps) -> ColorJitterParams:
@@ -659,6 +674,97 @@ def color_jitter_batch_host(images, steps, apply, ratio):
     _check(lib().ffcv_color_jitter_batch_host(_p(images), B, H, W, ctypes.byref(params), _p(apply), _p(ratio)),
            'ffcv_color_jitter_batch_host')
     return images
+
+
+def uniform_draw_batch(ids, loader_seed, epoch, op_id, p, lo, hi, apply, value, status=None, stream=None):
+    """``rand() < p`` then ``uniform(lo, hi)`` of the batch on the device (op id
+    9 grayscale, 10 solarization, 11 blur): apply uint8[B], value float64[B]."""
+    _check(lib().ffcv_uniform_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                         int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(op_id), float(p),
+                                         float(lo), float(hi), _p(apply), _p(value), _p(status)),
+           'ffcv_uniform_draw_batch')
+
+
+def uniform_draw_batch_host(ids, loader_seed, epoch, op_id, p, lo, hi):
+    """The same draws on the host: (apply uint8 (B,), value float64 (B,))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    apply = np.empty(ids.size, np.uint8)
+    value = np.empty(ids.size, np.float64)
+    _check(lib().ffcv_uniform_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+                                              int(epoch), int(op_id), float(p), float(lo), float(hi), _p(apply),
+                                              _p(value)), 'ffcv_uniform_draw_batch_host')
+    return apply, value
+
+
+BLUR_WROW = 32  # floats per sample in a blur weights array
+
+
+def blur_draw_batch(ids, loader_seed, epoch, p, sigma_lo, sigma_hi, ksize, apply, sigma, weights, status=None,
+                    stream=None):
+    """GaussianBlur's draws of the batch on the device (op id 11): apply
+    uint8[B], sigma float64[B], weights float32 (B, 32)."""
+    _check(lib().ffcv_blur_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                      int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p), float(sigma_lo),
+                                      float(sigma_hi), int(ksize), _p(apply), _p(sigma), _p(weights), _p(status)),
+           'ffcv_blur_draw_batch')
+
+
+def blur_draw_batch_host(ids, loader_seed, epoch, p, sigma_lo, sigma_hi, ksize):
+    """The same draws on the host: (apply uint8 (B,), sigma float64 (B,),
+    weights float32 (B, 32))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    apply = np.empty(ids.size, np.uint8)
+    sigma = np.empty(ids.size, np.float64)
+    weights = np.empty((ids.size, BLUR_WROW), np.float32)
+    _check(lib().ffcv_blur_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch),
+                                           float(p), float(sigma_lo), float(sigma_hi), int(ksize), _p(apply),
+                                           _p(sigma), _p(weights)), 'ffcv_blur_draw_batch_host')
+    return apply, sigma, weights
+
+
+def gaussian_blur_lds_bytes():
+    """15 * H * W of the largest image one workgroup of gaussian_blur_batch blurs whole."""
+    return int(lib().ffcv_gaussian_blur_lds_bytes())
+
+
+def gaussian_blur_band_rows():
+    """Output rows per workgroup beyond the whole-image regime."""
+    return int(lib().ffcv_gaussian_blur_band_rows())
+
+
+def gaussian_blur_strip_cols(height, width, ksize):
+    """Output columns per workgroup (== width while one strip serves a band)."""
+    return int(lib().ffcv_gaussian_blur_strip_cols(int(height), int(width), int(ksize)))
+
+
+def gaussian_blur_batch(src, dst, ksize, apply, weights, dst_stride=0, stream=None):
+    """Blur (apply[k] != 0) or copy each image of a dense device uint8
+    (B, H, W, 3) batch into ``dst`` (ffcv_gaussian_blur_batch): one launch, out
+    of place; apply device uint8 (B,), weights device float32 (B, 32)."""
+    if src.dim() != 4 or int(src.shape[3]) != 3 or src.element_size() != 1 or not src.is_contiguous():
+        raise TypeError('gaussian_blur_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
+    B, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    _check(lib().ffcv_gaussian_blur_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(ksize), _p(apply),
+                                          _p(weights), int(dst_stride)), 'ffcv_gaussian_blur_batch')
+    return dst
+
+
+def gaussian_blur_batch_host(src: np.ndarray, dst: np.ndarray, ksize, apply, weights, nthreads=1):
+    """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
+    if not (isinstance(src, np.ndarray) and isinstance(dst, np.ndarray) and src.dtype == np.uint8 and
+            dst.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3 and src.flags.c_contiguous and
+            dst.flags.c_contiguous and dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
+        raise TypeError('gaussian_blur_batch_host: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are '
+                        'required')
+    B, H, W = (int(x) for x in src.shape[:3])
+    apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
+    weights = np.ascontiguousarray(weights, np.float32)
+    if apply.size != B or weights.shape != (B, BLUR_WROW):
+        raise TypeError(f'gaussian_blur_batch_host: apply ({B},) and weights ({B}, {BLUR_WROW}) are required, got '
+                        f'{apply.shape} and {weights.shape}')
+    _check(lib().ffcv_gaussian_blur_batch_host(_p(src), _p(dst), B, H, W, int(ksize), _p(apply), _p(weights), 0,
+                                               int(max(1, nthreads))), 'ffcv_gaussian_blur_batch_host')
+    return dst[:B]
 
 
 MIXUP_U8, MIXUP_F32 = 1, 2  # FFCV_MIXUP_*

@@ -15,7 +15,8 @@ stages and generates stage functions with ``ast``.  Here:
    RandomTranslate (with RandomHorizontalFlip / Cutout in any order, then
    NormalizeImage(float16)) is lowered the same way into the small-image
    launch (``_lower_simple``).  A run of adjacent colour-jitter operations
-   becomes one launch of its own (``_lower_color``).  A RandomResizedCrop
+   (grayscale and solarization included) becomes one launch of its own
+   (``_lower_color``).  A RandomResizedCrop
    transform on device data absorbs the Cutout / RandomHorizontalFlip /
    NormalizeImage(float16) behind it (``_lower_rrc_transform``).
 3. ``collect_requirements`` walks states exactly like graph.py:295-354.  A
@@ -277,10 +278,11 @@ class Graph:
 
     def _lower_color(self, chain):
         """A run of adjacent RandomBrightness / RandomContrast /
-        RandomSaturation, each kind at most once: ONE device launch behind
-        the draws (ffcv_color_jitter_batch).  The first operation of the run
-        carries the program, the others run as identities; a repeated kind
-        starts a new run.  (To the decoder lowerings a colour-jitter
+        RandomSaturation / RandomGrayscale / RandomSolarization, each kind at
+        most once and at most three in all: ONE device launch behind the
+        draws (ffcv_color_jitter_batch).  The first operation of the run
+        carries the program, the others run as identities; a repeated kind,
+        or a fourth operation, starts a new run.  (To the decoder lowerings a colour-jitter
         operation is an unknown operation: it ends the fused prefix.)"""
         from ..transforms.color_jitter import _ColorJitter
         run = []
@@ -288,7 +290,7 @@ class Graph:
             if not isinstance(op, _ColorJitter) or len(self.operation_to_node[op]) != 1:
                 run = []
                 continue
-            if any(type(o) is type(op) for o in run):
+            if len(run) == 3 or any(type(o) is type(op) for o in run):
                 run = []
             run.append(op)
             if len(run) > 1:

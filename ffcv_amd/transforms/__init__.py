@@ -2,7 +2,9 @@ from .cutout import Cutout
 from .flip import RandomHorizontalFlip
 from .translate import RandomTranslate
 from .random_resized_crop import RandomResizedCrop
-from .color_jitter import RandomBrightness, RandomContrast, RandomSaturation
+from .color_jitter import (RandomBrightness, RandomContrast, RandomSaturation, RandomGrayscale,
+                           RandomSolarization)
+from .gaussian_blur import GaussianBlur
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .poison import Poison
 from .replace_label import ReplaceLabel
@@ -14,4 +16,5 @@ from .common import Squeeze
 __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 'Squeeze', 'View',
            'RandomResizedCrop', 'RandomHorizontalFlip', 'RandomTranslate', 'Cutout', 'ModuleWrapper',
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
+           'RandomGrayscale', 'RandomSolarization', 'GaussianBlur',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']

@@ -9,6 +9,12 @@ draw says so, blends the uint8 HWC image in float64 like the reference:
 (brightness), the mean of the image's uint8 gray values (contrast) or the
 pixel's own gray value (saturation).
 
+RandomGrayscale and RandomSolarization (op ids 9 and 10; the
+reference has neither) are two more operations of the same family: the same
+two draws, with ``uniform(0, 0)`` and ``uniform(threshold, threshold)``;
+grayscale sets every channel to the pixel's gray value (saturation at ratio
+0), solarization maps ``v >= threshold ? 255 - v : v``.
+
 On device tensors a run of adjacent colour-jitter operations is ONE
 ffcv_color_jitter_batch launch behind its draws (the graph lowering makes the
 first operation of the run carry the program); on host arrays each operation
@@ -60,6 +66,16 @@ def saturation_np(image, ratio):
     return image
 
 
+def grayscale_np(image, _ratio=0.0):
+    image[...] = gray_u8(image)[..., None]
+    return image
+
+
+def solarize_np(image, threshold):
+    image[...] = np.where(image >= threshold, 255 - image, image)
+    return image
+
+
 def jitter_range(magnitude):
     return max(0, 1 - magnitude), 1 + magnitude
 
@@ -95,6 +111,15 @@ class _ColorJitter(Operation):
         self._absorbed = False
         self._program = [self]  # the run this operation leads (graph lowering)
 
+    def draw_device(self, ctx, apply, ratio):
+        """The batch's decisions into device apply uint8[B] / ratio float64[B]."""
+        from .. import libffcv as L
+        L.color_jitter_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, self.op_id, self.p, self.magnitude,
+                                  apply, ratio, None, ctx.stream)
+
+    def draw_host(self, seed, epoch, sample):
+        return jitter_draw(seed, epoch, sample, self.op_id, self.p, self.magnitude)
+
     def generate_code(self) -> Callable:
         if self._absorbed:
             def fused(images, *_):
@@ -110,8 +135,7 @@ class _ColorJitter(Operation):
                 apply = ch.empty((n, B), dtype=ch.uint8, device=images.device)
                 ratio = ch.empty((n, B), dtype=ch.float64, device=images.device)
                 for i, op in enumerate(program):
-                    L.color_jitter_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, op.op_id, op.p,
-                                              op.magnitude, apply[i], ratio[i], None, ctx.stream)
+                    op.draw_device(ctx, apply[i], ratio[i])
                 ws = None
                 if int(images.shape[1]) * int(images.shape[2]) * 3 > L.color_jitter_lds_bytes() and \
                         any(op.kind == L.CJ_CONTRAST for op in program):
@@ -122,7 +146,7 @@ class _ColorJitter(Operation):
             arr = images.numpy() if isinstance(images, ch.Tensor) else images
             for i, sid in enumerate(indices):
                 for op in program:
-                    apply, ratio = jitter_draw(seed, epoch, sid, op.op_id, op.p, op.magnitude)
+                    apply, ratio = op.draw_host(seed, epoch, sid)
                     if apply:
                         type(op).host_fn(arr[i], ratio)
             return images
@@ -186,3 +210,68 @@ class RandomSaturation(_ColorJitter):
 
     def __init__(self, magnitude, p=0.5):
         super().__init__(magnitude, p)
+
+
+class _UniformDraw(_ColorJitter):
+    """A colour step whose second draw is ``uniform(lo, hi)`` with a range of
+    its own (ffcv_uniform_draw_batch)."""
+    lo = hi = 0.0
+
+    def __init__(self, p):
+        Operation.__init__(self)
+        try:
+            pf = float(p)
+        except (TypeError, ValueError):
+            raise ValueError(f'{type(self).__name__}: p must be a number, got {p!r}')
+        if not 0 <= pf <= 1:
+            raise ValueError(f'{type(self).__name__}: p must lie in [0, 1], got {p!r}')
+        self.p = p
+        self._absorbed = False
+        self._program = [self]
+
+    def draw_device(self, ctx, apply, ratio):
+        from .. import libffcv as L
+        L.uniform_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, self.op_id, self.p, self.lo, self.hi, apply,
+                             ratio, None, ctx.stream)
+
+    def draw_host(self, seed, epoch, sample):
+        rs = np.random.RandomState(contract_seed(seed, epoch, int(sample), self.op_id))
+        apply = bool(rs.rand() < self.p)
+        return apply, np.float64(rs.uniform(self.lo, self.hi))
+
+
+class RandomGrayscale(_UniformDraw):
+    """Randomly convert the image to gray (all three channels carry the
+    pixel's gray value). Operates on raw arrays (not tensors).
+
+    Parameters
+    ----------
+    p : float
+        probability to convert
+    """
+    op_id, kind, host_fn = 9, 4, staticmethod(grayscale_np)
+
+    def __init__(self, p=0.1):
+        super().__init__(p)
+
+
+class RandomSolarization(_UniformDraw):
+    """Randomly invert every byte at or above a threshold. Operates on raw
+    arrays (not tensors).
+
+    Parameters
+    ----------
+    threshold : int
+        bytes ``v >= threshold`` become ``255 - v``; in [0, 256]
+    p : float
+        probability to solarize
+    """
+    op_id, kind, host_fn = 10, 5, staticmethod(solarize_np)
+
+    def __init__(self, threshold=128, p=0.5):
+        import numbers
+        if isinstance(threshold, bool) or not isinstance(threshold, numbers.Integral) or not 0 <= threshold <= 256:
+            raise ValueError(f'RandomSolarization: threshold must be an int in [0, 256], got {threshold!r}')
+        super().__init__(p)
+        self.threshold = int(threshold)
+        self.lo = self.hi = float(self.threshold)

@@ -1,0 +1,112 @@
+"""GaussianBlur (the reference has no blur: the semantics are
+this project's own, pinned as arithmetic that numpy reproduces).
+
+Each sample draws ``rand() < p`` and then ``sigma = uniform(sigma_lo,
+sigma_hi)`` from its own MT19937 under the seeding contract (op id 11).  An
+applied uint8 (H, W, 3) image is convolved with the ``kernel_size`` normalised
+Gaussian weights of its sigma, rows then columns, in float32 with every
+product and sum rounded on its own, the border reflected (reflect-101), and
+rounded half to even back to uint8.
+
+On device tensors it is the draw launch plus ONE launch
+(ffcv_gaussian_blur_batch: a workgroup per image or per band of rows, the
+float32 intermediate in LDS); images that are not applied are copied by the
+same launch.  On host arrays it is the host twins over the Loader's threads.
+"""
+import math
+import numbers
+from dataclasses import replace
+from typing import Callable, Optional, Tuple
+
+import numpy as np
+import torch as ch
+
+from ..pipeline.allocation_query import AllocationQuery
+from ..pipeline.operation import Operation
+from ..pipeline.state import State
+from ..pipeline import runtime
+
+
+class GaussianBlur(Operation):
+    """Randomly blur the image with a Gaussian kernel of random sigma.
+    Operates on raw arrays (not tensors).
+
+    Parameters
+    ----------
+    kernel_size : int
+        Odd number of taps per axis, 1 to 31.
+    sigma : float or Tuple[float, float]
+        The standard deviation, or the (low, high) range it is drawn from.
+    p : float
+        probability to blur
+    """
+    device_aware = True
+    per_sample = True
+    op_id = 11
+
+    def __init__(self, kernel_size: int, sigma=(0.1, 2.0), p=0.5):
+        super().__init__()
+        if isinstance(kernel_size, bool) or not isinstance(kernel_size, numbers.Integral) or \
+                not 1 <= kernel_size <= 31 or kernel_size % 2 == 0:
+            raise ValueError(f'GaussianBlur: kernel_size must be an odd int in [1, 31], got {kernel_size!r}')
+        try:
+            lo, hi = (float(sigma),) * 2 if isinstance(sigma, numbers.Real) else (float(x) for x in sigma)
+            pf = float(p)
+        except (TypeError, ValueError):
+            raise ValueError(f'GaussianBlur: sigma must be a number or a (low, high) pair and p a number, got '
+                             f'{sigma!r}, {p!r}')
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi):
+            raise ValueError(f'GaussianBlur: sigma must be finite with 0 < low <= high, got {sigma!r}')
+        if not 0 <= pf <= 1:
+            raise ValueError(f'GaussianBlur: p must lie in [0, 1], got {p!r}')
+        self.kernel_size = int(kernel_size)
+        self.sigma = (lo, hi)
+        self.p = p
+
+    def generate_code(self) -> Callable:
+        from .. import libffcv as L
+        ksize, (lo, hi), p = self.kernel_size, self.sigma, self.p
+        key = ('gaussian_blur', id(self))
+
+        def gaussian_blur(images, dst, indices):
+            ctx = runtime.current()
+            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
+                if not images.is_contiguous():
+                    raise TypeError('GaussianBlur: a contiguous (B, H, W, 3) batch is required')
+                B = int(images.shape[0])
+                apply = ctx.device_buffer(key + ('apply',), ctx.batch_size, ch.uint8)
+                sigma = ctx.device_buffer(key + ('sigma',), ctx.batch_size, ch.float64)
+                weights = ctx.device_buffer(key + ('weights',), ctx.batch_size * L.BLUR_WROW, ch.float32)
+                L.blur_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, p, lo, hi, ksize, apply, sigma, weights,
+                                  None, ctx.stream)
+                out = dst[:B]
+                L.gaussian_blur_batch(images, out, ksize, apply, weights, 0, ctx.stream)
+                return out
+            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
+            src = images.numpy() if isinstance(images, ch.Tensor) else images
+            src = np.ascontiguousarray(src)
+            B = len(indices)
+            out = dst[:B]
+            out_np = out.numpy() if isinstance(out, ch.Tensor) else out
+            from ..pipeline.compiler import Compiler
+            apply, _, weights = L.blur_draw_batch_host(np.asarray(indices, np.uint64), seed, epoch, p, lo, hi, ksize)
+            L.gaussian_blur_batch_host(src[:B], out_np, ksize, apply, weights,
+                                       nthreads=max(1, int(Compiler.num_threads)))
+            return out
+        gaussian_blur.is_parallel = True
+        gaussian_blur.with_indices = True
+        return gaussian_blur
+
+    def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
+        dt, shape = previous_state.dtype, previous_state.shape
+        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
+        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
+            raise TypeError(f'GaussianBlur works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
+                            'place it before ToTorchImage / NormalizeImage / Convert')
+        if (self.kernel_size - 1) // 2 >= min(shape[0], shape[1]):
+            raise TypeError(f'GaussianBlur: kernel_size {self.kernel_size} reflects past a {shape[0]}x{shape[1]} '
+                            'image ((kernel_size - 1) / 2 must be below its height and width)')
+        if previous_state.device.type == 'cuda':
+            return (replace(previous_state, jit_mode=False),
+                    AllocationQuery(tuple(shape), dt, previous_state.device))
+        return (replace(previous_state, jit_mode=not isinstance(dt, ch.dtype)), AllocationQuery(tuple(shape), dt))

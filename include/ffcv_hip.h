@@ -576,7 +576,11 @@ int ffcv_color_jitter_draw_batch_host(const uint64_t *sample_ids, int batch,
 enum {
   FFCV_CJ_BRIGHTNESS = 1,
   FFCV_CJ_CONTRAST = 2,
-  FFCV_CJ_SATURATION = 3
+  FFCV_CJ_SATURATION = 3,
+  FFCV_CJ_GRAYSCALE = 4, /* every channel = gray(pixel): saturation at ratio 0
+                            (the step's ratio is not read) */
+  FFCV_CJ_SOLARIZE = 5   /* v >= threshold ? 255 - v : v per byte, the integer
+                            threshold in [0, 256] passed as the step's ratio */
 };
 
 typedef struct ffcv_color_jitter_params {
@@ -611,6 +615,82 @@ int ffcv_color_jitter_batch_host(uint8_t *images, int batch, int height,
                                  int width,
                                  const ffcv_color_jitter_params *params,
                                  const uint8_t *apply, const double *ratio);
+
+/* ------------------------- grayscale / solarization / Gaussian blur --- */
+/* RandomGrayscale, RandomSolarization and GaussianBlur (the
+ * reference has none of them, the semantics are this project's own).  Seeding
+ * contract op ids: 9 grayscale, 10 solarization, 11 blur.  All three draw
+ * like colour jitter: apply = rand() < p, then value = uniform(lo, hi), both
+ * always drawn, in that order.
+ *
+ * The draws of grayscale (lo = hi = 0) and solarization (lo = hi =
+ * threshold); their pixels are steps FFCV_CJ_GRAYSCALE / FFCV_CJ_SOLARIZE of
+ * ffcv_color_jitter_batch.  op_id must be 9, 10 or 11, p in [0, 1], lo <= hi
+ * finite; apply / value / status as in ffcv_color_jitter_draw_batch. */
+int ffcv_uniform_draw_batch(void *stream, const uint64_t *sample_ids,
+                            int batch, uint64_t loader_seed, uint64_t epoch,
+                            int op_id, double p, double lo, double hi,
+                            uint8_t *apply, double *value, int32_t *status);
+int ffcv_uniform_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                 uint64_t loader_seed, uint64_t epoch,
+                                 int op_id, double p, double lo, double hi,
+                                 uint8_t *apply, double *value);
+
+/* The blur's draws (op id 11) in one launch: the decision, sigma =
+ * uniform(sigma_lo, sigma_hi) and the sample's float32 weights, a row of 32
+ * floats per sample with entries [ksize, 32) zero.  In float64, with k =
+ * ksize: e_j = exp(-0.5 (t_j t_j)), t_j = (j - (k - 1) / 2) / sigma; s = the
+ * sum of e_j in ascending j; w_j = float32(e_j / s), stored as +0 where it
+ * lies below 2^-126.  exp is the one function not pinned bit for bit.
+ *   ksize : odd, 1 .. 31;  0 < sigma_lo <= sigma_hi, finite
+ *   apply : uint8[B];  sigma : float64[B];  weights : float32[B][32]
+ *   status : int32[B] or NULL (device entry only) */
+int ffcv_blur_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                         uint64_t loader_seed, uint64_t epoch, double p,
+                         double sigma_lo, double sigma_hi, int ksize,
+                         uint8_t *apply, double *sigma, float *weights,
+                         int32_t *status);
+int ffcv_blur_draw_batch_host(const uint64_t *sample_ids, int batch,
+                              uint64_t loader_seed, uint64_t epoch, double p,
+                              double sigma_lo, double sigma_hi, int ksize,
+                              uint8_t *apply, double *sigma, float *weights);
+
+/* Separable blur of a dense device [B][height][width][3] uint8 batch, out of
+ * place, in ONE launch; image k is written at dst + k * dst_stride_bytes (0 =
+ * dense).  Image k is blurred with weights[k][0 .. ksize) where apply[k] != 0
+ * and copied otherwise.  All pixel arithmetic is float32, every product and
+ * sum rounded on its own (never fused), border reflect-101:
+ *   h(y, x) = w_0 v(y, x - r) + w_1 v(y, x - r + 1) + ...   (ascending j)
+ *   out     = uint8(clip(rint(w_0 h(y - r, x) + w_1 h(y - r + 1, x) + ...)))
+ * with r = (ksize - 1) / 2 and rint rounding half to even; the weights must
+ * be finite (the kernel also multiplies pixels by padding weights of +0, which
+ * changes no finite sum).  Any byte
+ * alignment of src and dst; loads are 16-byte aligned chunks holding at
+ * least one byte of an image, so the allocation of src must extend to the
+ * 16-byte boundaries around it (the rule of ffcv_gather_rows).
+ * Two regimes: while 15 * height * width <= ffcv_gaussian_blur_lds_bytes()
+ * a workgroup owns an image; larger images are cut into bands of
+ * ffcv_gaussian_blur_band_rows() rows, and a band too wide for a workgroup's
+ * LDS into column strips of ffcv_gaussian_blur_strip_cols(height, width,
+ * ksize) columns (== width while one strip serves).  Supported sizes: height
+ * and width up to 65535.
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, sizes <= 0 or
+ * beyond 65535, an even ksize or one outside 1 .. 31, (ksize - 1) / 2 >=
+ * min(height, width), a dst_stride_bytes smaller than an image, or src and dst
+ * ranges that overlap (dst == src included). */
+int ffcv_gaussian_blur_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                             int batch, int height, int width, int ksize,
+                             const uint8_t *apply, const float *weights,
+                             uint64_t dst_stride_bytes);
+/* The same on host memory over nthreads threads, compiled from the kernel's
+ * pixel functions. */
+int ffcv_gaussian_blur_batch_host(const uint8_t *src, uint8_t *dst, int batch,
+                                  int height, int width, int ksize,
+                                  const uint8_t *apply, const float *weights,
+                                  uint64_t dst_stride_bytes, int nthreads);
+uint64_t ffcv_gaussian_blur_lds_bytes(void);
+uint64_t ffcv_gaussian_blur_band_rows(void);
+uint64_t ffcv_gaussian_blur_strip_cols(int height, int width, int ksize);
 
 /* --------------------------------------------------------- mixup ------ */
 /* mixup.py: ImageMixup.  Sample i of a dense [n_samples][sample_elems] array
