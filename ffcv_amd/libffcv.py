@@ -182,6 +182,16 @@ _SIGS = {
     'ffcv_gaussian_blur_lds_bytes': (c_uint64, []),
     'ffcv_gaussian_blur_band_rows': (c_uint64, []),
     'ffcv_gaussian_blur_strip_cols': (c_uint64, [c_int, c_int, c_int]),
+    'ffcv_hue_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_void_p,
+                                    c_void_p, c_void_p]),
+    'ffcv_hue_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_void_p,
+                                         c_void_p]),
+    'ffcv_color_jitter_joint_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p]),
+    'ffcv_color_jitter_joint_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p,
+                                                        c_void_p, c_void_p]),
+    'ffcv_hue_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'ffcv_hue_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ffcv_mixup_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int]),
     'ffcv_mixup_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int,
                                       c_int]),
@@ -765,6 +775,88 @@ def gaussian_blur_batch_host(src: np.ndarray, dst: np.ndarray, ksize, apply, wei
     _check(lib().ffcv_gaussian_blur_batch_host(_p(src), _p(dst), B, H, W, int(ksize), _p(apply), _p(weights), 0,
                                                int(max(1, nthreads))), 'ffcv_gaussian_blur_batch_host')
     return dst[:B]
+
+
+def hue_draw_batch(ids, loader_seed, epoch, p, magnitude, apply, shift, status=None, stream=None):
+    """RandomHue's decisions of the batch on the device (op id 12): apply
+    uint8[B], shift float64[B] = uniform(-magnitude, magnitude)."""
+    _check(lib().ffcv_hue_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                     int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p), float(magnitude),
+                                     _p(apply), _p(shift), _p(status)), 'ffcv_hue_draw_batch')
+
+
+def hue_draw_batch_host(ids, loader_seed, epoch, p, magnitude):
+    """The same draws on the host: (apply uint8 (B,), shift float64 (B,))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    apply = np.empty(ids.size, np.uint8)
+    shift = np.empty(ids.size, np.float64)
+    _check(lib().ffcv_hue_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch),
+                                          float(p), float(magnitude), _p(apply), _p(shift)),
+           'ffcv_hue_draw_batch_host')
+    return apply, shift
+
+
+def _magnitude4(magnitude):
+    m = np.ascontiguousarray([float(x) for x in magnitude], dtype=np.float64)
+    if m.shape != (4,):
+        raise TypeError('four magnitudes (brightness, contrast, saturation, hue) are required')
+    return m
+
+
+def color_jitter_joint_rows(magnitude):
+    """Rows the joint draw writes: the components with a non-zero magnitude."""
+    return sum(1 for x in magnitude if float(x) != 0.0)
+
+
+def color_jitter_joint_draw_batch(ids, loader_seed, epoch, p, magnitude, apply, ratio, status=None, stream=None):
+    """RandomColorJitter's five draws of the batch on the device (op id 13):
+    one row of apply uint8 (rows, B) / ratio float64 (rows, B) per component of
+    (brightness, contrast, saturation, hue) with a non-zero magnitude."""
+    m = _magnitude4(magnitude)
+    _check(lib().ffcv_color_jitter_joint_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                                    int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p),
+                                                    _p(m), _p(apply), _p(ratio), _p(status)),
+           'ffcv_color_jitter_joint_draw_batch')
+
+
+def color_jitter_joint_draw_batch_host(ids, loader_seed, epoch, p, magnitude):
+    """The same draws on the host: (apply uint8 (rows, B), ratio float64 (rows, B))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    m = _magnitude4(magnitude)
+    rows = color_jitter_joint_rows(m)
+    apply = np.empty((max(rows, 1), ids.size), np.uint8)
+    ratio = np.empty((max(rows, 1), ids.size), np.float64)
+    _check(lib().ffcv_color_jitter_joint_draw_batch_host(_p(ids), int(ids.size),
+                                                         int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p),
+                                                         _p(m), _p(apply), _p(ratio)),
+           'ffcv_color_jitter_joint_draw_batch_host')
+    return apply[:rows], ratio[:rows]
+
+
+def hue_batch(images, apply, shift, stream=None):
+    """The hue shift in place on a device uint8 (B, H, W, 3) batch, one launch:
+    image k turns by shift[k] where apply[k] != 0 (apply uint8 (B,), shift
+    float64 (B,), both on the device)."""
+    if images.dim() != 4 or int(images.shape[3]) != 3 or images.element_size() != 1 or not images.is_contiguous():
+        raise TypeError('hue_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
+    B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    _check(lib().ffcv_hue_batch(_stream(stream), _p(images), B, H, W, _p(apply), _p(shift)), 'ffcv_hue_batch')
+    return images
+
+
+def hue_batch_host(images, apply, shift):
+    """The same in place on a C-contiguous numpy uint8 (B, H, W, 3)."""
+    if not (isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.flags.c_contiguous
+            and images.ndim == 4 and images.shape[3] == 3):
+        raise TypeError('hue_batch_host: a C-contiguous uint8 (B, H, W, 3) array is required')
+    B, H, W = (int(x) for x in images.shape[:3])
+    apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
+    shift = np.ascontiguousarray(shift, np.float64).reshape(-1)
+    if apply.size != B or shift.size != B:
+        raise TypeError(f'hue_batch_host: apply ({B},) and shift ({B},) are required, got {apply.shape} and '
+                        f'{shift.shape}')
+    _check(lib().ffcv_hue_batch_host(_p(images), B, H, W, _p(apply), _p(shift)), 'ffcv_hue_batch_host')
+    return images
 
 
 MIXUP_U8, MIXUP_F32 = 1, 2  # FFCV_MIXUP_*

@@ -5,6 +5,7 @@ from .random_resized_crop import RandomResizedCrop
 from .color_jitter import (RandomBrightness, RandomContrast, RandomSaturation, RandomGrayscale,
                            RandomSolarization)
 from .gaussian_blur import GaussianBlur
+from .hue import RandomHue, RandomColorJitter
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .poison import Poison
 from .replace_label import ReplaceLabel
@@ -16,5 +17,5 @@ from .common import Squeeze
 __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 'Squeeze', 'View',
            'RandomResizedCrop', 'RandomHorizontalFlip', 'RandomTranslate', 'Cutout', 'ModuleWrapper',
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
-           'RandomGrayscale', 'RandomSolarization', 'GaussianBlur',
+           'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomHue', 'RandomColorJitter',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']

@@ -692,6 +692,74 @@ uint64_t ffcv_gaussian_blur_lds_bytes(void);
 uint64_t ffcv_gaussian_blur_band_rows(void);
 uint64_t ffcv_gaussian_blur_strip_cols(int height, int width, int ksize);
 
+/* ------------------------------- hue, jointly gated colour jitter ----- */
+/* RandomHue and RandomColorJitter (the reference has neither,
+ * the semantics are this project's own).  Seeding contract op ids: 12 hue,
+ * 13 joint colour jitter.
+ *
+ * Hue's draws: apply = rand() < p, then shift = uniform(-magnitude,
+ * magnitude), both always drawn, in that order.  p in [0, 1], magnitude
+ * finite in [0, 0.5]; sample_ids / apply / shift / status as in
+ * ffcv_color_jitter_draw_batch. */
+int ffcv_hue_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                        uint64_t loader_seed, uint64_t epoch, double p,
+                        double magnitude, uint8_t *apply, double *shift,
+                        int32_t *status);
+int ffcv_hue_draw_batch_host(const uint64_t *sample_ids, int batch,
+                             uint64_t loader_seed, uint64_t epoch, double p,
+                             double magnitude, uint8_t *apply, double *shift);
+
+/* The joint draws: five values from ONE stream per sample, always all five:
+ * rand() < p, then uniform(max(0, 1 - m), 1 + m) for m = magnitude[0]
+ * (brightness), [1] (contrast), [2] (saturation), then uniform(-magnitude[3],
+ * magnitude[3]) (hue).  magnitude is a HOST array of four: the first three
+ * finite and >= 0, the fourth finite in [0, 0.5].  One row of apply / ratio is
+ * written per component with a non-zero magnitude, compacted in the order
+ * brightness, contrast, saturation, hue; every apply row carries the one
+ * decision.  The brightness / contrast / saturation rows are thus the
+ * [n_steps][B] arrays ffcv_color_jitter_batch takes for the program of the
+ * active components, and the hue row, the last, is what ffcv_hue_batch takes.
+ *   apply : uint8[rows][B];  ratio : float64[rows][B], rows <= 4
+ *   status : int32[B] or NULL (device entry only) */
+int ffcv_color_jitter_joint_draw_batch(void *stream,
+                                       const uint64_t *sample_ids, int batch,
+                                       uint64_t loader_seed, uint64_t epoch,
+                                       double p, const double *magnitude,
+                                       uint8_t *apply, double *ratio,
+                                       int32_t *status);
+int ffcv_color_jitter_joint_draw_batch_host(const uint64_t *sample_ids,
+                                            int batch, uint64_t loader_seed,
+                                            uint64_t epoch, double p,
+                                            const double *magnitude,
+                                            uint8_t *apply, double *ratio);
+
+/* The hue shift in place on a device [B][height][width][3] uint8 batch, in ONE
+ * launch; image k is turned by shift[k] (|shift[k]| <= 0.5) where apply[k] !=
+ * 0 and is neither read nor written otherwise.  Per pixel, with integers r, g,
+ * b and D = float32(float64(6) * shift[k]), all else float32 with every
+ * operation rounded on its own (never fused), `/` the correctly rounded IEEE
+ * division:
+ *   mx, mn = max, min of (r, g, b);  c = mx - mn;  c == 0: unchanged
+ *   C = float32(c);  V = float32(mx)
+ *   (num, base) = (g - b, 0) if mx == r, else (b - r, 2) if mx == g, else
+ *                 (r - g, 4)
+ *   x = base + float32(num) / C;  x = x + D
+ *   x = x < 0 ? x + 6 : x;  then  x = x >= 6 ? x - 6 : x
+ *   i = floor(x);  f = x - i;  s = C / V
+ *   P = V * (1 - s);  Q = V * (1 - s * f);  T = V * (1 - s * (1 - f))
+ *   (R, G, B) for i = 0 .. 5: (V,T,P) (Q,V,P) (P,V,T) (P,Q,V) (T,P,V) (V,P,Q)
+ *   out = uint8(rint(value)), rint rounding half to even
+ * Any byte alignment of images; loads are 16-byte aligned chunks holding at
+ * least one byte of an applied image (the rule of ffcv_gather_rows), and no
+ * byte outside an applied image is written.
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, sizes <= 0 or
+ * 3 * height * width > 2^31 - 1. */
+int ffcv_hue_batch(void *stream, uint8_t *images, int batch, int height,
+                   int width, const uint8_t *apply, const double *shift);
+/* The same on host memory, compiled from the kernel's pixel function. */
+int ffcv_hue_batch_host(uint8_t *images, int batch, int height, int width,
+                        const uint8_t *apply, const double *shift);
+
 /* --------------------------------------------------------- mixup ------ */
 /* mixup.py: ImageMixup.  Sample i of a dense [n_samples][sample_elems] array
  * belongs to batch s = i / batch_size, of length min(batch_size, n_samples -
