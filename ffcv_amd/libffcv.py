@@ -192,6 +192,19 @@ _SIGS = {
                                                         c_void_p, c_void_p]),
     'ffcv_hue_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ffcv_hue_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'ffcv_affine_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p, c_int,
+                                       c_int, c_void_p, c_void_p, c_void_p]),
+    'ffcv_affine_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p, c_int, c_int,
+                                            c_void_p, c_void_p]),
+    'ffcv_affine_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_uint64]),
+    'ffcv_affine_batch_host': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_uint64, c_int]),
+    'ffcv_affine_whole_bytes': (c_uint64, []),
+    'ffcv_affine_tile_rows': (c_uint64, []),
+    'ffcv_affine_tile_cols': (c_uint64, []),
+    'ffcv_affine_tile_lds': (c_uint64, []),
+    'ffcv_affine_tile_bytes': (c_uint64, [c_int, c_int, c_int, c_void_p, c_int, c_int]),
     'ffcv_mixup_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int]),
     'ffcv_mixup_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int,
                                       c_int]),
@@ -857,6 +870,101 @@ def hue_batch_host(images, apply, shift):
                         f'{shift.shape}')
     _check(lib().ffcv_hue_batch_host(_p(images), B, H, W, _p(apply), _p(shift)), 'ffcv_hue_batch_host')
     return images
+
+
+AFFINE_BILINEAR, AFFINE_NEAREST = 0, 1  # FFCV_AFFINE_*
+AFFINE_NOT_STAGEABLE = (1 << 64) - 1    # ffcv_affine_tile_bytes: relative coordinates leave 32 bits
+
+
+def _ranges12(ranges):
+    r = np.ascontiguousarray([float(x) for x in ranges], dtype=np.float64)
+    if r.shape != (12,):
+        raise TypeError('six (low, high) pairs (angle, tx, ty, scale, shear x, shear y) are required')
+    return r
+
+
+def _fill3(fill):
+    f = np.ascontiguousarray(fill, dtype=np.uint8).reshape(-1)
+    if f.shape != (3,):
+        raise TypeError('fill must be three uint8 values')
+    return f
+
+
+def affine_draw_batch(ids, loader_seed, epoch, p, ranges, height, width, apply, coef, status=None, stream=None):
+    """RandomAffine's seven draws of the batch and their Q16 coefficients on
+    the device (op id 14): apply uint8[B], coef int64 (B, 6)."""
+    r = _ranges12(ranges)
+    _check(lib().ffcv_affine_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                        int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p), _p(r),
+                                        int(height), int(width), _p(apply), _p(coef), _p(status)),
+           'ffcv_affine_draw_batch')
+
+
+def affine_draw_batch_host(ids, loader_seed, epoch, p, ranges, height, width):
+    """The same draws on the host: (apply uint8 (B,), coef int64 (B, 6))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    r = _ranges12(ranges)
+    apply = np.empty(ids.size, np.uint8)
+    coef = np.empty((ids.size, 6), np.int64)
+    _check(lib().ffcv_affine_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+                                             int(epoch), float(p), _p(r), int(height), int(width), _p(apply),
+                                             _p(coef)), 'ffcv_affine_draw_batch_host')
+    return apply, coef
+
+
+def affine_whole_bytes():
+    """3 * H * W of the largest image one workgroup of affine_batch warps whole."""
+    return int(lib().ffcv_affine_whole_bytes())
+
+
+def affine_tile_shape():
+    """(rows, columns) of an output tile beyond the whole-image regime."""
+    return int(lib().ffcv_affine_tile_rows()), int(lib().ffcv_affine_tile_cols())
+
+
+def affine_tile_lds():
+    """Bytes of staged source beyond which a tile reads global memory directly."""
+    return int(lib().ffcv_affine_tile_lds())
+
+
+def affine_tile_bytes(height, width, mode, coef, tile_row, tile_col):
+    """Bytes the kernel stages for one tile (0: it reads nothing;
+    AFFINE_NOT_STAGEABLE: its coordinates leave 32 bits)."""
+    q = np.ascontiguousarray(coef, dtype=np.int64).reshape(-1)
+    if q.shape != (6,):
+        raise TypeError('six coefficients are required')
+    return int(lib().ffcv_affine_tile_bytes(int(height), int(width), int(mode), _p(q), int(tile_row), int(tile_col)))
+
+
+def affine_batch(src, dst, mode, fill, apply, coef, dst_stride=0, stream=None):
+    """Warp (apply[k] != 0) or copy each image of a dense device uint8
+    (B, H, W, 3) batch into ``dst`` (ffcv_affine_batch): one launch, out of
+    place; apply device uint8 (B,), coef device int64 (B, 6)."""
+    if src.dim() != 4 or int(src.shape[3]) != 3 or src.element_size() != 1 or not src.is_contiguous():
+        raise TypeError('affine_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
+    B, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    f = _fill3(fill)
+    _check(lib().ffcv_affine_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef),
+                                   int(dst_stride)), 'ffcv_affine_batch')
+    return dst
+
+
+def affine_batch_host(src: np.ndarray, dst: np.ndarray, mode, fill, apply, coef, nthreads=1):
+    """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
+    if not (isinstance(src, np.ndarray) and isinstance(dst, np.ndarray) and src.dtype == np.uint8 and
+            dst.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3 and src.flags.c_contiguous and
+            dst.flags.c_contiguous and dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
+        raise TypeError('affine_batch_host: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are required')
+    B, H, W = (int(x) for x in src.shape[:3])
+    f = _fill3(fill)
+    apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
+    coef = np.ascontiguousarray(coef, np.int64)
+    if apply.size != B or coef.shape != (B, 6):
+        raise TypeError(f'affine_batch_host: apply ({B},) and coef ({B}, 6) are required, got {apply.shape} and '
+                        f'{coef.shape}')
+    _check(lib().ffcv_affine_batch_host(_p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef), 0,
+                                        int(max(1, nthreads))), 'ffcv_affine_batch_host')
+    return dst[:B]
 
 
 MIXUP_U8, MIXUP_F32 = 1, 2  # FFCV_MIXUP_*

@@ -6,6 +6,7 @@ from .color_jitter import (RandomBrightness, RandomContrast, RandomSaturation, R
                            RandomSolarization)
 from .gaussian_blur import GaussianBlur
 from .hue import RandomHue, RandomColorJitter
+from .affine import RandomAffine, RandomRotation
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .poison import Poison
 from .replace_label import ReplaceLabel
@@ -18,4 +19,5 @@ __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 
            'RandomResizedCrop', 'RandomHorizontalFlip', 'RandomTranslate', 'Cutout', 'ModuleWrapper',
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
            'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomHue', 'RandomColorJitter',
+           'RandomAffine', 'RandomRotation',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']

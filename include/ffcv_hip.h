@@ -760,6 +760,96 @@ int ffcv_hue_batch(void *stream, uint8_t *images, int batch, int height,
 int ffcv_hue_batch_host(uint8_t *images, int batch, int height, int width,
                         const uint8_t *apply, const double *shift);
 
+/* ------------------------------------- affine warp (rotation, shear) -- */
+/* RandomAffine and RandomRotation (the reference has neither,
+ * the semantics are this project's own).  Seeding contract op id: 14.
+ *
+ * The draws: seven values from one stream per sample, always all seven:
+ * apply = rand() < p, angle = uniform(r0, r1) in degrees, tx =
+ * rint(uniform(r2, r3)), ty = rint(uniform(r4, r5)), s = uniform(r6, r7),
+ * shx = uniform(r8, r9), shy = uniform(r10, r11) in degrees, with r = ranges,
+ * a HOST array of six (low, high) pairs; uniform is lo + (hi - lo) * rand(),
+ * rint rounds half to even.  The matrix, in float64, every operation rounded
+ * on its own, K = 0.017453292519943295, for height x width images:
+ *   rot = angle K;  sx = shx K;  sy = shy K
+ *   a = cos(rot - sy) / cos(sy)
+ *   b = -(cos(rot - sy) tan(sx) / cos(sy)) - sin(rot)
+ *   c = sin(rot - sy) / cos(sy)
+ *   d = -(sin(rot - sy) tan(sx) / cos(sy)) + cos(rot)
+ *   m00 = d / s;  m01 = -b / s;  m10 = -c / s;  m11 = a / s
+ *   cx = (width - 1) / 2;  cy = (height - 1) / 2
+ *   b0 = (m00 (-cx - tx) + m01 (-cy - ty)) + cx
+ *   b1 = (m10 (-cx - tx) + m11 (-cy - ty)) + cy
+ * and coef[k] = int64(rint(v * 65536)) of (m00, m01, b0, m10, m11, b1).  sin,
+ * cos and tan are the functions not pinned bit for bit.
+ *   ranges : finite, low <= high; angle within -360 .. 360, tx within -width
+ *            .. width, ty within -height .. height, scale within 1/16 .. 16,
+ *            both shears within -60 .. 60
+ *   height, width : 1 .. 32767;  p in [0, 1]
+ *   apply : uint8[B] (written even where p == 1);  coef : int64[B][6]
+ *   status : int32[B] or NULL (device entry only) */
+#define FFCV_AFFINE_BILINEAR 0
+#define FFCV_AFFINE_NEAREST 1
+int ffcv_affine_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                           uint64_t loader_seed, uint64_t epoch, double p,
+                           const double *ranges, int height, int width,
+                           uint8_t *apply, int64_t *coef, int32_t *status);
+int ffcv_affine_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                uint64_t loader_seed, uint64_t epoch, double p,
+                                const double *ranges, int height, int width,
+                                uint8_t *apply, int64_t *coef);
+
+/* The warp of a dense device [B][height][width][3] uint8 batch, out of place,
+ * in ONE launch; image k is written at dst + k * dst_stride_bytes (0 = dense),
+ * warped by q = coef[k] where apply[k] != 0 and copied otherwise.  Integers
+ * only, in int64, for output column c and row r:
+ *   X = q0 c + q1 r + q2;  Y = q3 c + q4 r + q5
+ * a tap outside 0 <= iy < height, 0 <= ix < width takes the channel's fill
+ * (a HOST array of three), each tap tested on its own; shifts are arithmetic.
+ *   nearest:  out = tap((Y + 32768) >> 16, (X + 32768) >> 16)
+ *   bilinear: ix = X >> 16, iy = Y >> 16, fx = (X & 0xFFFF) >> 8, fy alike
+ *             top = (256 - fx) tap(iy, ix) + fx tap(iy, ix + 1)
+ *             bot = the same on row iy + 1
+ *             out = ((256 - fy) top + fy bot + 32768) >> 16
+ * An image whose coefficients have |q0|, |q1|, |q3| or |q4| above 2^23, or
+ * |q2| or |q5| above 2^40, comes out all fill.  Any byte alignment of src and
+ * dst; loads are 16-byte aligned chunks holding at least one byte of an image
+ * (the rule of ffcv_gather_rows); no byte outside dst's image ranges is
+ * written.  While 3 * height * width <= ffcv_affine_whole_bytes() a workgroup
+ * owns an image and stages it in LDS; larger images are cut into tiles of
+ * ffcv_affine_tile_rows() x ffcv_affine_tile_cols() outputs, and a tile stages
+ * its source footprint while that takes at most ffcv_affine_tile_lds() bytes
+ * and reads its taps from global memory otherwise.
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, sizes outside
+ * 1 .. 32767, 3 * height * width > 2^31 - 1, a mode other than the two, a
+ * dst_stride_bytes smaller than an image, or src and dst ranges that overlap
+ * (dst == src included). */
+int ffcv_affine_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                      int batch, int height, int width, int mode,
+                      const uint8_t *fill, const uint8_t *apply,
+                      const int64_t *coef, uint64_t dst_stride_bytes);
+/* The same on host memory over nthreads threads, compiled from the kernel's
+ * pixel function. */
+int ffcv_affine_batch_host(const uint8_t *src, uint8_t *dst, int batch,
+                           int height, int width, int mode,
+                           const uint8_t *fill, const uint8_t *apply,
+                           const int64_t *coef, uint64_t dst_stride_bytes,
+                           int nthreads);
+uint64_t ffcv_affine_whole_bytes(void);
+uint64_t ffcv_affine_tile_rows(void);
+uint64_t ffcv_affine_tile_cols(void);
+uint64_t ffcv_affine_tile_lds(void);
+/* The bytes the kernel stages for tile (tile_row, tile_col) of a height x
+ * width image under coef (a HOST array of six) and mode, from the kernel's own
+ * footprint code: 0 for a tile that reads nothing (its footprint misses the
+ * image; coefficients outside the bounds; invalid arguments), 2^64 - 1 for a
+ * footprint whose relative coordinates leave 32 bits.  The tile reads global
+ * memory directly when the value exceeds ffcv_affine_tile_lds() (beyond the
+ * whole-image regime, where the value is the image's chunks). */
+uint64_t ffcv_affine_tile_bytes(int height, int width, int mode,
+                                const int64_t *coef, int tile_row,
+                                int tile_col);
+
 /* --------------------------------------------------------- mixup ------ */
 /* mixup.py: ImageMixup.  Sample i of a dense [n_samples][sample_elems] array
  * belongs to batch s = i / batch_size, of length min(batch_size, n_samples -
