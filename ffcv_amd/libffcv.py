@@ -79,6 +79,11 @@ class ColorJitterParams(ctypes.Structure):
     _fields_ = [('n_steps', c_int32), ('steps', ctypes.c_uint8 * 4)]
 
 
+class ToneParams(ctypes.Structure):
+    """ffcv_tone_params: FFCV_TONE_* kinds in pipeline order, posterize's bits."""
+    _fields_ = [('n_steps', c_int32), ('steps', ctypes.c_uint8 * 4), ('bits', c_int32)]
+
+
 _lib = None
 
 _SIGS = {
@@ -192,6 +197,14 @@ _SIGS = {
                                                         c_void_p, c_void_p]),
     'ffcv_hue_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ffcv_hue_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'ffcv_tone_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    'ffcv_tone_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_void_p]),
+    'ffcv_tone_workspace_bytes': (c_uint64, [c_int]),
+    'ffcv_tone_lds_bytes': (c_uint64, []),
+    'ffcv_tone_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_uint64]),
+    'ffcv_tone_batch_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'ffcv_tone_tables_host': (c_int, [c_int, c_int, c_void_p, c_void_p, c_int]),
     'ffcv_affine_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p, c_int,
                                        c_int, c_void_p, c_void_p, c_void_p]),
     'ffcv_affine_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p, c_int, c_int,
@@ -870,6 +883,90 @@ def hue_batch_host(images, apply, shift):
                         f'{shift.shape}')
     _check(lib().ffcv_hue_batch_host(_p(images), B, H, W, _p(apply), _p(shift)), 'ffcv_hue_batch_host')
     return images
+
+
+TONE_POSTERIZE, TONE_AUTOCONTRAST, TONE_EQUALIZE, TONE_INVERT = 1, 2, 3, 4  # FFCV_TONE_*
+
+
+def tone_params(steps, bits=8) -> ToneParams:
+    """The program of FFCV_TONE_* kinds in pipeline order (and posterize's bits)."""
+    p = ToneParams()
+    p.n_steps = len(steps)
+    for i, st in enumerate(list(steps)[:4]):
+        p.steps[i] = int(st)
+    p.bits = int(bits)
+    return p
+
+
+def _tone_pairs(op_ids, ps):
+    ops = np.ascontiguousarray([int(o) for o in op_ids], dtype=np.int32)
+    ps = np.ascontiguousarray([float(x) for x in ps], dtype=np.float64)
+    if ops.size != ps.size:
+        raise TypeError(f'as many probabilities as op ids are required, got {ops.size} and {ps.size}')
+    return ops, ps
+
+
+def tone_draw_batch(ids, loader_seed, epoch, op_ids, ps, apply, status=None, stream=None):
+    """The decisions of up to four table operations (op id 15 posterize, 16
+    autocontrast, 17 equalize, 18 invert) of the batch in one launch:
+    apply uint8 (n, B), row i ``rand() < ps[i]`` from the stream of op_ids[i]."""
+    ops, ps = _tone_pairs(op_ids, ps)
+    _check(lib().ffcv_tone_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
+                                      int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(ops.size), _p(ops),
+                                      _p(ps), _p(apply), _p(status)), 'ffcv_tone_draw_batch')
+
+
+def tone_draw_batch_host(ids, loader_seed, epoch, op_ids, ps):
+    """The same draws on the host: apply uint8 (n, B)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    ops, ps = _tone_pairs(op_ids, ps)
+    apply = np.empty((max(int(ops.size), 1), ids.size), np.uint8)
+    _check(lib().ffcv_tone_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch),
+                                           int(ops.size), _p(ops), _p(ps), _p(apply)), 'ffcv_tone_draw_batch_host')
+    return apply
+
+
+def tone_workspace_bytes(batch):
+    return int(lib().ffcv_tone_workspace_bytes(int(batch)))
+
+
+def tone_lds_bytes():
+    return int(lib().ffcv_tone_lds_bytes())
+
+
+def tone_batch(images, steps, bits, apply, workspace=None, stream=None):
+    """The program ``steps`` in place on a device uint8 (B, H, W, 3) batch
+    (apply uint8 (n, B)); one launch while an image fits tone_lds_bytes(), else
+    one without and two with an autocontrast or equalize step."""
+    if images.dim() != 4 or int(images.shape[3]) != 3 or images.element_size() != 1 or not images.is_contiguous():
+        raise TypeError('tone_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
+    B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    params = steps if isinstance(steps, ToneParams) else tone_params(steps, bits)
+    wb = int(workspace.numel() * workspace.element_size()) if workspace is not None else 0
+    _check(lib().ffcv_tone_batch(_stream(stream), _p(images), B, H, W, ctypes.byref(params), _p(apply),
+                                 _p(workspace), wb), 'ffcv_tone_batch')
+
+
+def tone_batch_host(images, steps, bits, apply):
+    """The same program in place on a C-contiguous numpy uint8 (B, H, W, 3)."""
+    if not (isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.flags.c_contiguous
+            and images.ndim == 4 and images.shape[3] == 3):
+        raise TypeError('tone_batch_host: a C-contiguous uint8 (B, H, W, 3) array is required')
+    B, H, W = (int(x) for x in images.shape[:3])
+    params = steps if isinstance(steps, ToneParams) else tone_params(steps, bits)
+    apply = np.ascontiguousarray(apply, np.uint8).reshape(max(params.n_steps, 1), B)
+    _check(lib().ffcv_tone_batch_host(_p(images), B, H, W, ctypes.byref(params), _p(apply)), 'ffcv_tone_batch_host')
+    return images
+
+
+def tone_tables_host(kind, bits, hists):
+    """The host twin's table builder: uint8 (n, 256) tables of step ``kind``
+    for channels with the uint32 (n, 256) histograms ``hists``."""
+    hists = np.ascontiguousarray(hists, dtype=np.uint32).reshape(-1, 256)
+    tables = np.empty(hists.shape, np.uint8)
+    _check(lib().ffcv_tone_tables_host(int(kind), int(bits), _p(hists), _p(tables), int(hists.shape[0])),
+           'ffcv_tone_tables_host')
+    return tables
 
 
 AFFINE_BILINEAR, AFFINE_NEAREST = 0, 1  # FFCV_AFFINE_*

@@ -16,8 +16,9 @@ stages and generates stage functions with ``ast``.  Here:
    NormalizeImage(float16)) is lowered the same way into the small-image
    launch (``_lower_simple``).  A run of adjacent colour-jitter operations
    (grayscale and solarization included) becomes one launch of its own
-   (``_lower_color``).  A RandomResizedCrop
-   transform on device data absorbs the Cutout / RandomHorizontalFlip /
+   (``_lower_color``), and so does a run of adjacent table operations
+   (posterize, autocontrast, equalize, invert: ``_lower_tone``).  A
+   RandomResizedCrop transform on device data absorbs the Cutout / RandomHorizontalFlip /
    NormalizeImage(float16) behind it (``_lower_rrc_transform``).
 3. ``collect_requirements`` walks states exactly like graph.py:295-354.  A
    non-device-aware (user) operation that would receive device data gets an
@@ -157,6 +158,7 @@ class Graph:
             return
         for chain in self._chains.values():
             self._lower_color(chain)
+            self._lower_tone(chain)
         for name, chain in self._chains.items():
             if chain and type(chain[0]) is SimpleRGBImageDecoder:
                 self._lower_simple(chain)
@@ -291,6 +293,25 @@ class Graph:
                 run = []
                 continue
             if len(run) == 3 or any(type(o) is type(op) for o in run):
+                run = []
+            run.append(op)
+            if len(run) > 1:
+                op._absorbed = True
+                run[0]._program = list(run)
+
+    def _lower_tone(self, chain):
+        """A run of adjacent RandomPosterize / RandomAutocontrast /
+        RandomEqualize / RandomInvert, each type at most once (so at most
+        four): ONE draw launch and ONE ffcv_tone_batch.  The first operation
+        of the run carries the program, the others run as identities; a
+        repeated type starts a new run."""
+        from ..transforms.tone import _Tone
+        run = []
+        for op in chain:
+            if not isinstance(op, _Tone) or len(self.operation_to_node[op]) != 1:
+                run = []
+                continue
+            if len(run) == 4 or any(type(o) is type(op) for o in run):
                 run = []
             run.append(op)
             if len(run) > 1:

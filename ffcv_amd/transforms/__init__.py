@@ -7,6 +7,7 @@ from .color_jitter import (RandomBrightness, RandomContrast, RandomSaturation, R
 from .gaussian_blur import GaussianBlur
 from .hue import RandomHue, RandomColorJitter
 from .affine import RandomAffine, RandomRotation
+from .tone import RandomPosterize, RandomAutocontrast, RandomEqualize, RandomInvert
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .poison import Poison
 from .replace_label import ReplaceLabel
@@ -20,4 +21,5 @@ __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
            'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomHue', 'RandomColorJitter',
            'RandomAffine', 'RandomRotation',
+           'RandomPosterize', 'RandomAutocontrast', 'RandomEqualize', 'RandomInvert',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']

@@ -8,7 +8,8 @@ op ids: 1 crop (the crop decoders), 2 cutout, 3 flip, 4 translate,
 its own id, so that a pipeline with a crop decoder and the transform does not
 draw the same stream twice), 9 grayscale, 10 solarization, 11 blur, 12 hue,
 13 joint colour jitter (RandomColorJitter: five draws from one stream),
-14 affine (RandomAffine and RandomRotation: seven draws from one stream).  The
+14 affine (RandomAffine and RandomRotation: seven draws from one stream),
+15 posterize, 16 autocontrast, 17 equalize, 18 invert (one draw each).  The
 device kernels use the same function
 (csrc/device_common.h sample_seed).  The reference itself draws from numba's
 per-thread generators seeded from OS entropy (nondeterministic); see

@@ -930,6 +930,80 @@ int ffcv_replace_label_batch(void *stream, int64_t *labels, int64_t n,
                              const uint64_t *poison_ids, int64_t n_poison,
                              int64_t new_label);
 
+/* ------------------- posterize / autocontrast / equalize / invert ------ */
+/* RandomPosterize, RandomAutocontrast, RandomEqualize and RandomInvert
+ * (the reference has none of them, the semantics are Pillow's
+ * ImageOps).  Each is a 256-entry byte table per image and channel, applied
+ * in place to a uint8 [H][W][3] image; autocontrast's table depends on the
+ * channel's first and last occupied value, equalize's on its histogram.
+ * Seeding contract op ids: 15 posterize, 16 autocontrast, 17 equalize,
+ * 18 invert; each operation makes ONE draw per sample, rand() < p. */
+enum {
+  FFCV_TONE_POSTERIZE = 1,    /* v & ~(2 ** (8 - bits) - 1) */
+  FFCV_TONE_AUTOCONTRAST = 2, /* ImageOps.autocontrast, cutoff 0 */
+  FFCV_TONE_EQUALIZE = 3,     /* ImageOps.equalize, no mask */
+  FFCV_TONE_INVERT = 4        /* 255 - v */
+};
+
+typedef struct ffcv_tone_params {
+  int32_t n_steps;  /* 1..4 */
+  uint8_t steps[4]; /* FFCV_TONE_* in pipeline order, each at most once */
+  int32_t bits;     /* posterize's bits, 1..8 (read when the program has a
+                       POSTERIZE step) */
+} ffcv_tone_params;
+
+/* The decisions of n operations (1..4) in one launch: apply[i * batch + k] =
+ * rand() < p[i] from sample k's own stream of op id op_ids[i] (15..18).
+ * op_ids and p are HOST arrays of n.
+ *   sample_ids : device uint64[B];  apply : device uint8[n][B] out
+ *   status     : device int32[B] out (FFCV_SAMPLE_RNG when a stream ran out),
+ *                or NULL */
+int ffcv_tone_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                         uint64_t loader_seed, uint64_t epoch, int n,
+                         const int32_t *op_ids, const double *p,
+                         uint8_t *apply, int32_t *status);
+/* The same draws on host arrays (the CPU-device Loader). */
+int ffcv_tone_draw_batch_host(const uint64_t *sample_ids, int batch,
+                              uint64_t loader_seed, uint64_t epoch, int n,
+                              const int32_t *op_ids, const double *p,
+                              uint8_t *apply);
+
+/* Bytes of workspace ffcv_tone_batch needs for `batch` images of any size
+ * (3 x 256 uint32 counters per image; only a program with an AUTOCONTRAST or
+ * EQUALIZE step on images beyond the one-workgroup regime uses it, every
+ * other call may pass NULL / 0). */
+uint64_t ffcv_tone_workspace_bytes(int batch);
+/* The largest image (height * width * 3 bytes) one workgroup keeps in LDS:
+ * up to this size a program is ONE launch, beyond it one launch without and
+ * two launches with an AUTOCONTRAST or EQUALIZE step. */
+uint64_t ffcv_tone_lds_bytes(void);
+/* The program in place on a device [B][height][width][3] uint8 batch at any
+ * byte alignment; step i of image k runs when apply[i * batch + k] != 0, on
+ * the previous step's result, exactly as the separate operations would (the
+ * launch composes the applied steps' tables on the image's histogram and
+ * touches the pixels once).  An image none of whose steps applies is neither
+ * read nor written.
+ *   apply     : device uint8[n_steps][B]
+ *   workspace : device, 4-byte aligned, >= ffcv_tone_workspace_bytes (zeroed
+ *               on the stream by the call), or NULL where unused
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, a
+ * non-positive shape, an image over 2^31 - 1 bytes, n_steps outside 1..4, an
+ * unknown or repeated step, bits outside 1..8 with a POSTERIZE step, and a
+ * missing, misaligned or short workspace where it is used.  batch == 0
+ * returns FFCV_OK. */
+int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height,
+                    int width, const ffcv_tone_params *params,
+                    const uint8_t *apply, void *workspace,
+                    uint64_t workspace_bytes);
+/* The same program on host memory, compiled from the same table functions as
+ * the kernels (csrc/tone_common.h) and composed the same way. */
+int ffcv_tone_batch_host(uint8_t *images, int batch, int height, int width,
+                         const ffcv_tone_params *params, const uint8_t *apply);
+/* The host twin's table builder: tables[j][v] of step `kind` (bits read by
+ * POSTERIZE) for a channel whose 256-bin histogram is hists[j], j < n. */
+int ffcv_tone_tables_host(int kind, int bits, const uint32_t *hists,
+                          uint8_t *tables, int n);
+
 #ifdef __cplusplus
 }
 #endif
