@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "device_common.h"
+#include "lds_stage.h"  // lds_chunks
 
 #define FFCV_AFFINE_OP 14
 #define FFCV_AFFINE_M_MAX ((int64_t)1 << 23)  // |q0|, |q1|, |q3|, |q4| at most
@@ -148,9 +149,6 @@ struct AffineMemTap {
   }
 };
 
-// 16-byte chunks that can hold `bytes` contiguous bytes at any alignment
-FFCV_HD uint32_t affine_chunks(uint32_t bytes) { return (bytes + 30u) >> 4; }
-
 // The source footprint of output rows [y0, y1) x columns [x0, x1) under q:
 // the bounding box of the four corners' (iy, ix) -- X and Y are linear in (c,
 // r), so their extremes over the rectangle are at its corners, and the shifts
@@ -169,7 +167,7 @@ struct AffineBox {
   FFCV_HD uint32_t staged_bytes(int W) const {
     if (empty()) return 0;
     const uint32_t nrows = (uint32_t)(hi - lo), cw = (uint32_t)(ch - cl);
-    return cw == (uint32_t)W ? affine_chunks(nrows * 3u * cw) * 16u : nrows * affine_chunks(3u * cw) * 16u;
+    return cw == (uint32_t)W ? lds_chunks(nrows * 3u * cw) * 16u : nrows * lds_chunks(3u * cw) * 16u;
   }
 };
 

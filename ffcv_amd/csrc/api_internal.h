@@ -24,3 +24,56 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
     hipError_t _e = hipGetLastError();                               \
     if (_e != hipSuccess) return ffcv::check_hip(_e, what);          \
   } while (0)
+
+// ---- shared by the entries of the uint8 HWC image transforms --------------
+namespace ffcv {
+
+// The argument check of an entry that takes a batch of dense uint8
+// [batch][height][width][3] images of at most 2^31 - 1 bytes each; pointers:
+// every pointer argument the entry needs is there.
+inline bool u8_images_ok(const char *who, bool pointers, int batch, int height, int width) {
+  if (batch < 0 || !pointers || height <= 0 || width <= 0 || (uint64_t)height * (uint64_t)width * 3 > 0x7fffffffull) {
+    set_error("%s: invalid arguments (batch %d, %dx%d)", who, batch, height, width);
+    return false;
+  }
+  return true;
+}
+
+// How a pixel-run launch (lds_stage.h) cuts images of npx pixels: the whole
+// image per workgroup when its bytes fit lds_bytes, else tiles of tile_px.
+inline bool run_tiling(const char *who, int batch, uint64_t npx, uint32_t lds_bytes, uint32_t tile_px,
+                       uint32_t *tile_px_out, uint32_t *ntiles, unsigned *blocks) {
+  *tile_px_out = npx * 3 <= lds_bytes ? (uint32_t)npx : tile_px;
+  const uint64_t nt = (npx + *tile_px_out - 1) / *tile_px_out, nb = (uint64_t)batch * nt;
+  if (nb > 0x7fffffffull) {
+    set_error("%s: %llu workgroups exceed one launch", who, (unsigned long long)nb);
+    return false;
+  }
+  *ntiles = (uint32_t)nt;
+  *blocks = (unsigned)nb;
+  return true;
+}
+
+// A draw kernel, one lane per sample: kernel(args...) over `batch` samples.
+template <class K, class... A>
+int launch_draw(const char *name, K kernel, void *stream, int batch, A... args) {
+  if (batch == 0) return FFCV_OK;
+  hipLaunchKernelGGL(kernel, dim3((batch + 63) / 64), dim3(64), 0, as_stream(stream), args...);
+  FFCV_LAUNCH_CHECK(name);
+  return FFCV_OK;
+}
+
+// The host twin of a draw: draw_one(k) for every sample, non-zero when the
+// sample's random stream ran out.
+template <class F>
+int host_draw(const char *who, int batch, F draw_one) {
+  int err = 0;
+  for (int k = 0; k < batch; k++) err |= draw_one(k);
+  if (err) {
+    set_error("%s: MT19937 stream exhausted", who);
+    return FFCV_EINVAL;
+  }
+  return FFCV_OK;
+}
+
+}  // namespace ffcv

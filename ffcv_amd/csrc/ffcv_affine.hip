@@ -8,10 +8,9 @@
 //
 //   fill:   the coefficients lie outside the bounds, or the tile's source
 //           footprint (affine_box) misses the image: nothing is read.
-//   LDS:    the footprint's rows are staged as uint8 in LDS with 16-byte
-//           aligned global loads whatever the byte offset, one byte range per
-//           row (one range for all when they span the image's width).  Taps
-//           are aligned LDS dwords joined by v_alignbyte; the two horizontal
+//   LDS:    the footprint's rows are staged as uint8 in LDS, a tile of rows
+//           (lds_stage.h): one byte range per row, one for all when they span
+//           the image's width.  Taps are lds_pixel reads; the two horizontal
 //           taps of a bilinear sample are six contiguous bytes, three dwords.
 //           Coordinates are 32-bit, relative to the footprint's corner, which
 //           affine_box has shown exact.
@@ -21,10 +20,10 @@
 //
 // Every thread computes four adjacent pixels at a time, twelve bytes, into an
 // LDS copy of the tile's output, dense, walking the coordinates by one add
-// per pixel; those bytes leave as 16-byte aligned stores at any alignment of
-// dst, and the chunks cut by a row's (or the tile's) ends byte by byte.  An
-// image whose apply flag is 0 is the identity under nearest: its footprint is
-// the tile itself, and the staged bytes leave as they came: a copy.
+// per pixel; those bytes leave by the row tile's write-back at any alignment
+// of dst.  An image whose apply flag is 0 is the identity under nearest: its
+// footprint is the tile itself, and the staged bytes leave as they came: a
+// copy.
 //
 //   whole image: 3 H W <= AFFINE_WHOLE_BYTES -- one tile per image, the image
 //     staged once as one byte range.
@@ -84,21 +83,17 @@ static AffinePlan affine_plan(int H, int W) {
   P.tw = P.whole ? W : std::min(W, AFFINE_TILE_COLS);
   P.nty = (H + P.th - 1) / P.th;
   P.ntx = (W + P.tw - 1) / P.tw;
-  P.budget = P.whole ? affine_chunks(3u * H * W) * 16u : AFFINE_TILE_LDS;
+  P.budget = P.whole ? lds_chunks(3u * H * W) * 16u : AFFINE_TILE_LDS;
   P.out_off = 16u + P.budget + 16u;
   P.lds = P.out_off + ((3u * P.th * P.tw + 15u) & ~15u) + 32u;
   return P;
 }
 
-// Taps from the staged footprint; coordinates relative to its corner.
-struct AffineLdsTap {
-  const uint8_t *base;  // first staged chunk
-  int pitch, lead0, stepmod, nrows, cw;
+// Taps from the staged footprint (a tile of rows, lds_stage.h); coordinates
+// relative to its corner.
+struct AffineLdsTap : LdsRows<true> {
+  int nrows, cw;
   uint32_t fill;
-  // r < 2^15, pitch < 2^17 and the product lies inside LDS: 24-bit multiplies (full rate)
-  FFCV_DEV const uint8_t *row(int r) const {
-    return base + __umul24((uint32_t)r, (uint32_t)pitch) + ((lead0 + __umul24((uint32_t)r, (uint32_t)stepmod)) & 15);
-  }
   // v where ok, else fill, as masks: a select whose operands are both computed
   // keeps the LDS reads out of branches, so the reads of a thread's four
   // pixels can be in flight together
@@ -106,12 +101,9 @@ struct AffineLdsTap {
     const uint32_t m = 0u - (uint32_t)ok;
     return (v & 0xffffffu & m) | (fill & ~m);
   }
-  // R | G << 8 | B << 16 from two ALIGNED 4-byte LDS reads joined by v_alignbyte
   FFCV_DEV uint32_t one(int iy, int ix) const {
     const bool ok = (uint32_t)iy < (uint32_t)nrows && (uint32_t)ix < (uint32_t)cw;
-    const uint8_t *a = row(ok ? iy : 0) + 3 * (ok ? ix : 0);
-    const uint32_t *qa = (const uint32_t *)__builtin_align_down(a, 4);
-    return pick(ok, __builtin_amdgcn_alignbyte(qa[1], qa[0], (uint32_t)(a - (const uint8_t *)qa)));
+    return pick(ok, lds_pixel(row(ok ? iy : 0) + 3 * (ok ? ix : 0)));
   }
   // (iy, ix) and (iy, ix + 1): six contiguous bytes from three aligned dwords.
   // The column is clamped to [-1, cw - 1] for the address only (16 bytes lie in
@@ -194,9 +186,7 @@ __global__ void __launch_bounds__(AFFINE_THREADS)
                        int mode, uint32_t fill, const uint8_t *__restrict__ apply, const int64_t *__restrict__ coef,
                        AffinePlan P) {
   extern __shared__ uint4 affine_smem[];
-  typedef uint32_t bx4_t __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(1))) bx4_t gx4_t;
-  bx4_t *s_u8 = (bx4_t *)affine_smem + 1;  // staged chunks, behind 16 bytes a tap at column -1 may read
+  lds_x4_t *s_u8 = (lds_x4_t *)affine_smem + 1;  // staged chunks, behind 16 bytes a tap at column -1 may read
   uint32_t *s_out = (uint32_t *)((uint8_t *)affine_smem + P.out_off);
   const int t = threadIdx.x;
   const uint32_t per = (uint32_t)P.nty * P.ntx;
@@ -231,34 +221,19 @@ __global__ void __launch_bounds__(AFFINE_THREADS)
   const uint64_t step = (uint64_t)W * 3u;
   const uint8_t *img = src + (uint64_t)k * H * step;
   const int npix = rows * tc;
-  // where the write-back finds range y: wb + y * wb_pitch + ((wb_lead0 + y * wb_stepmod) & 15)
-  const uint8_t *wb = (const uint8_t *)s_out;
-  int wb_pitch = 3 * tc, wb_lead0 = 0, wb_stepmod = 0;
+  // where the write-back finds range y: the tile's dense output bytes
+  LdsRows<> wb = {(const uint8_t *)s_out, 3 * tc, 0, 0};
   if (regime == 1) {
-    // ---- stage source rows [lo, hi) x columns [cl, ch): one contiguous byte
-    // range when they span the width, else a range per row in whole chunks;
-    // 16-byte aligned loads (an aligned chunk holding a byte of a range never
-    // crosses a page)
+    // ---- stage source rows [lo, hi) x columns [cl, ch) as a tile of rows (lds_stage.h)
     const int nrows = box.hi - box.lo, cw = box.ch - box.cl;
     const uint64_t src0 = (uint64_t)(uintptr_t)img + ((uint64_t)box.lo * W + box.cl) * 3u;
     const bool span = cw == W;
     const int n_srows = span ? 1 : nrows;
     const uint32_t srow_bytes = span ? (uint32_t)nrows * 3u * W : 3u * cw;
-    const int nchr = (int)affine_chunks(srow_bytes);
-    for (int i = t; i < n_srows * nchr; i += AFFINE_THREADS) {
-      const int rr = i / nchr, c = i - rr * nchr;
-      const uint64_t ra = src0 + (uint64_t)rr * step;
-      if (c < (int)(((ra & 15) + srow_bytes + 15) >> 4)) s_u8[i] = ((gx4_t *)(uintptr_t)(ra & ~(uint64_t)15))[c];
-    }
+    const int nchr = (int)lds_chunks(srow_bytes);
+    stage_rows<AFFINE_THREADS>(t, src0, step, n_srows, srow_bytes, nchr, s_u8);
     __syncthreads();
-    AffineLdsTap tap;
-    tap.base = (const uint8_t *)s_u8;
-    tap.pitch = span ? 3 * W : nchr * 16;
-    tap.lead0 = (int)(src0 & 15);
-    tap.stepmod = span ? 0 : (int)(step & 15);
-    tap.nrows = nrows;
-    tap.cw = cw;
-    tap.fill = fill;
+    const AffineLdsTap tap{lds_rows<true>(s_u8, src0, step, span, nchr), nrows, cw, fill};
     if (on) {
       // 32-bit coordinates relative to the footprint's corner: the true values
       // fit (box.fits32), so wrapping arithmetic gives them exactly
@@ -272,10 +247,7 @@ __global__ void __launch_bounds__(AFFINE_THREADS)
         return affine_sample<int32_t>(md, (int32_t)w.X, (int32_t)w.Y, tap);
       });
     } else {
-      wb = tap.base;
-      wb_pitch = tap.pitch;
-      wb_lead0 = tap.lead0;
-      wb_stepmod = tap.stepmod;
+      wb = {tap.base, tap.pitch, tap.lead0, tap.stepmod};  // a copy: the staged rows
     }
   } else if (regime == 2) {
     AffineMemTap tap;
@@ -298,39 +270,12 @@ __global__ void __launch_bounds__(AFFINE_THREADS)
   __syncthreads();
 
   // ---- write back: the tile's bytes are in LDS, dense (warped) or as staged
-  // (a copy).  Rows that span the width leave as one byte range.  Whole
-  // 16-byte chunks of dst inside a range are one store, assembled from five
-  // aligned LDS dwords; the chunks cut by its ends go byte by byte.
+  // (a copy).  Rows that span the width leave as one byte range.
   const bool ospan = tc == W;
   const int n_orows = ospan ? 1 : rows;
   const uint32_t orow_bytes = ospan ? (uint32_t)rows * 3u * W : 3u * tc;
-  const int onch = (int)affine_chunks(orow_bytes);
   const uint64_t dst0 = (uint64_t)(uintptr_t)dst + (uint64_t)k * dst_stride + ((uint64_t)y0 * W + x0) * 3u;
-  for (int i = t; i < n_orows * onch; i += AFFINE_THREADS) {
-    const int y = i / onch, c = i - y * onch;
-    const uint64_t da = dst0 + (uint64_t)y * step;
-    const int dl = (int)(da & 15), c0 = 16 * c;  // the range is bytes [dl, dl + orow_bytes) of the aligned row
-    if (c0 >= dl + (int)orow_bytes) continue;
-    uint8_t *gb = (uint8_t *)(uintptr_t)(da & ~(uint64_t)15) + c0;
-    const uint8_t *sr = wb + y * wb_pitch + ((wb_lead0 + y * wb_stepmod) & 15);
-    if (c0 >= dl && c0 + 16 <= dl + (int)orow_bytes) {
-      const uint8_t *sp = sr + (c0 - dl);
-      const uint32_t *qq = (const uint32_t *)__builtin_align_down(sp, 4);
-      const uint32_t sh = (uint32_t)(sp - (const uint8_t *)qq);
-      const uint32_t q0 = qq[0], q1 = qq[1], q2 = qq[2], q3 = qq[3], q4 = qq[4];
-      bx4_t o;
-      o.x = __builtin_amdgcn_alignbyte(q1, q0, sh);
-      o.y = __builtin_amdgcn_alignbyte(q2, q1, sh);
-      o.z = __builtin_amdgcn_alignbyte(q3, q2, sh);
-      o.w = __builtin_amdgcn_alignbyte(q4, q3, sh);
-      *(gx4_t *)gb = o;
-    } else {
-      for (int j = 0; j < 16; j++) {
-        const int b = c0 + j - dl;
-        if (b >= 0 && b < (int)orow_bytes) gb[j] = sr[b];
-      }
-    }
-  }
+  write_back_rows<AFFINE_THREADS>(t, dst0, step, n_orows, orow_bytes, [&](int y) { return wb.row(y); });
 }
 
 namespace {
@@ -423,27 +368,19 @@ int ffcv_affine_draw_batch(void *stream, const uint64_t *sample_ids, int batch, 
                            int32_t *status) {
   if (!affine_draw_args_ok("ffcv_affine_draw_batch", sample_ids, batch, p, ranges, height, width, apply, coef))
     return FFCV_EINVAL;
-  if (batch == 0) return FFCV_OK;
   AffineRanges rg;
   std::memcpy(rg.v, ranges, sizeof(rg.v));
-  hipLaunchKernelGGL(affine_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream), sample_ids,
-                     batch, loader_seed, epoch, p, rg, height, width, apply, coef, status);
-  FFCV_LAUNCH_CHECK("affine_draw_kernel");
-  return FFCV_OK;
+  return ffcv::launch_draw("affine_draw_kernel", affine_draw_kernel, stream, batch, sample_ids, batch, loader_seed,
+                           epoch, p, rg, height, width, apply, coef, status);
 }
 
 int ffcv_affine_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch, double p,
                                 const double *ranges, int height, int width, uint8_t *apply, int64_t *coef) {
   if (!affine_draw_args_ok("ffcv_affine_draw_batch_host", sample_ids, batch, p, ranges, height, width, apply, coef))
     return FFCV_EINVAL;
-  int err = 0;
-  for (int k = 0; k < batch; k++)
-    err |= draw_affine(k, sample_ids[k], loader_seed, epoch, p, ranges, height, width, apply, coef);
-  if (err) {
-    ffcv::set_error("ffcv_affine_draw_batch_host: MT19937 stream exhausted");
-    return FFCV_EINVAL;
-  }
-  return FFCV_OK;
+  return ffcv::host_draw("ffcv_affine_draw_batch_host", batch, [&](int k) {
+    return draw_affine(k, sample_ids[k], loader_seed, epoch, p, ranges, height, width, apply, coef);
+  });
 }
 
 uint64_t ffcv_affine_whole_bytes(void) { return AFFINE_WHOLE_BYTES; }

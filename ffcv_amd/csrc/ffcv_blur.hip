@@ -1,14 +1,12 @@
 // ffcv_blur.hip -- GaussianBlur on a dense uint8 batch [B][H][W][3] (one
-// launch behind its draw launch), the draws of RandomGrayscale /
-// RandomSolarization / GaussianBlur (op ids 9-11), and the host twins.
+// launch behind its draw launch), its draw (op id 11), and the host twins.
 //
 // One kernel serves both regimes.  A 256-thread workgroup owns a tile of
 // output rows [y0, y1) x columns [x0, x1) of one image:
 //
 //   1. it stages the tile's source, rows [y0 - r, y1 + r) x columns
-//      [x0 - r, x1 + r) clipped to the image, as uint8 in LDS, with 16-byte
-//      aligned global loads whatever the byte offset (rows that span the
-//      image's width are one contiguous byte range and staged as one);
+//      [x0 - r, x1 + r) clipped to the image, as uint8 in LDS: a tile of rows
+//      (the scheme of lds_stage.h; rows that span the width are one range);
 //   2. horizontal pass: one float32 per staged row and tile column and
 //      channel into an LDS plane, border columns reflected at read time, a
 //      thread per four adjacent columns;
@@ -40,6 +38,7 @@
 
 #include "api_internal.h"
 #include "blur_common.h"
+#include "lds_stage.h"
 
 #define BLUR_THREADS 256
 #define BLUR_LDS_BYTES 32768  // whole-image regime: 15 H W at most this
@@ -48,17 +47,6 @@
 #define BLUR_MAX_DIM 65535   // largest supported height and width
 // the weights in LDS: up to 31 and the +0 padding of a four-output walk (34 floats in all), in whole chunks
 #define BLUR_W_LDS 144
-
-__global__ void __launch_bounds__(64) uniform_draw_kernel(const uint64_t *__restrict__ ids, int B,
-                                                          uint64_t loader_seed, uint64_t epoch, uint32_t op_id,
-                                                          double p, double lo, double hi,
-                                                          uint8_t *__restrict__ apply, double *__restrict__ value,
-                                                          int32_t *__restrict__ status) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= B) return;
-  const int err = draw_color_jitter(k, ids[k], loader_seed, epoch, op_id, p, lo, hi, apply, value);
-  if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
-}
 
 __global__ void __launch_bounds__(64) blur_draw_kernel(const uint64_t *__restrict__ ids, int B,
                                                        uint64_t loader_seed, uint64_t epoch, double p, double lo,
@@ -70,9 +58,6 @@ __global__ void __launch_bounds__(64) blur_draw_kernel(const uint64_t *__restric
   const int err = draw_blur(k, ids[k], loader_seed, epoch, p, lo, hi, ksize, apply, sigma, weights);
   if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
 }
-
-// 16-byte chunks that can hold `bytes` contiguous bytes at any alignment
-FFCV_HD uint32_t blur_chunks(uint32_t bytes) { return (bytes + 30u) >> 4; }
 
 // How a launch cuts an image into tiles, and the LDS a workgroup takes.
 struct BlurPlan {
@@ -89,7 +74,7 @@ static void blur_tile_lds(int H, int W, int rows, int cols, int r, uint32_t *u8_
   // chunks than its rows take apart, from two rows on; one row is the same
   // either way).  A copy stages one range of at most rows x cols pixels:
   // never more than this.
-  const uint32_t one = blur_chunks(nrows * 3u * cw) * 16u, apart = nrows * blur_chunks(3u * cw) * 16u;
+  const uint32_t one = lds_chunks(nrows * 3u * cw) * 16u, apart = nrows * lds_chunks(3u * cw) * 16u;
   const uint32_t staged = cols >= W ? one : std::max(one, apart);
   *u8_bytes = staged + 32u;  // + the pixel reads' and the output chunks' look-ahead
   *lds = BLUR_W_LDS + *u8_bytes + nrows * (uint32_t)cols * 12u;
@@ -146,10 +131,11 @@ __global__ void __launch_bounds__(BLUR_THREADS)
   const int lo = max(0, y0 - r), hi = min(H, y1 + r), cl = max(0, x0 - r), ch = min(W, x1 + r);
   const int nrows = hi - lo, cw = ch - cl, rows = y1 - y0, tc = x1 - x0;
 
-  // ---- stage source rows [lo, hi) x columns [cl, ch): one contiguous byte
-  // range when they span the width, else a range per row in whole chunks;
-  // 16-byte aligned loads (an aligned chunk holding a byte of a range never
-  // crosses a page).  A copy needs no halo and no columns: the band's rows
+  // ---- stage source rows [lo, hi) x columns [cl, ch).  This and the write
+  // back are the row-tile scheme of lds_stage.h written out: on the helpers
+  // the copy path measured slower (profiles/lds_stage_ab.txt).  One contiguous
+  // byte range when the rows span the width, else a range per row in whole
+  // chunks.  A copy needs no halo and no columns: the band's rows
   // are one byte range of the image, and the band's workgroups (one per
   // strip) take an equal piece of it each, never more than a tile's bytes.
   const uint64_t step = (uint64_t)W * 3u;
@@ -161,7 +147,7 @@ __global__ void __launch_bounds__(BLUR_THREADS)
   const bool span = !on || cw == W;
   const int n_srows = span ? 1 : nrows;
   const uint32_t srow_bytes = !on ? cp_len : (span ? (uint32_t)nrows * 3u * W : 3u * cw);
-  const int nchr = (int)blur_chunks(srow_bytes);
+  const int nchr = (int)lds_chunks(srow_bytes);
   const int pitch = span ? 3 * W : nchr * 16;  // LDS bytes from a staged row to the next
   const int lead0 = (int)(src0 & 15), stepmod = span ? 0 : (int)(step & 15);
   for (int i = t; i < n_srows * nchr; i += BLUR_THREADS) {
@@ -262,7 +248,7 @@ __global__ void __launch_bounds__(BLUR_THREADS)
   const bool ospan = !on || tc == W;
   const int n_orows = ospan ? 1 : rows;
   const uint32_t orow_bytes = !on ? cp_len : (ospan ? band_bytes : 3u * tc);
-  const int onch = (int)blur_chunks(orow_bytes);
+  const int onch = (int)lds_chunks(orow_bytes);
   const uint64_t dst0 = (uint64_t)(uintptr_t)dst + (uint64_t)k * dst_stride +
                         (on ? ((uint64_t)y0 * W + x0) * 3u : (uint64_t)y0 * step + cp0);
   for (int i = t; i < n_orows * onch; i += BLUR_THREADS) {
@@ -292,16 +278,6 @@ __global__ void __launch_bounds__(BLUR_THREADS)
 }
 
 namespace {
-
-bool uniform_args_ok(const char *who, const void *ids, int batch, int op_id, double p, double lo, double hi,
-                     const void *apply, const void *value) {
-  if (batch < 0 || !ids || !apply || !value || op_id < 9 || op_id > 11 || !(p >= 0.0 && p <= 1.0) ||
-      !std::isfinite(lo) || !std::isfinite(hi) || !(lo <= hi)) {
-    ffcv::set_error("%s: invalid arguments (op_id %d, p %g, range %g .. %g)", who, op_id, p, lo, hi);
-    return false;
-  }
-  return true;
-}
 
 bool blur_draw_args_ok(const char *who, const void *ids, int batch, double p, double lo, double hi, int ksize,
                        const void *apply, const void *sigma, const void *weights) {
@@ -375,43 +351,14 @@ void blur_image_host(const uint8_t *in, uint8_t *out, int H, int W, int ksize, c
 // ---------------------------------------------------------- C ABI -------
 extern "C" {
 
-int ffcv_uniform_draw_batch(void *stream, const uint64_t *sample_ids, int batch, uint64_t loader_seed,
-                            uint64_t epoch, int op_id, double p, double lo, double hi, uint8_t *apply,
-                            double *value, int32_t *status) {
-  if (!uniform_args_ok("ffcv_uniform_draw_batch", sample_ids, batch, op_id, p, lo, hi, apply, value))
-    return FFCV_EINVAL;
-  if (batch == 0) return FFCV_OK;
-  hipLaunchKernelGGL(uniform_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream), sample_ids,
-                     batch, loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, value, status);
-  FFCV_LAUNCH_CHECK("uniform_draw_kernel");
-  return FFCV_OK;
-}
-
-int ffcv_uniform_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch,
-                                 int op_id, double p, double lo, double hi, uint8_t *apply, double *value) {
-  if (!uniform_args_ok("ffcv_uniform_draw_batch_host", sample_ids, batch, op_id, p, lo, hi, apply, value))
-    return FFCV_EINVAL;
-  int err = 0;
-  for (int k = 0; k < batch; k++)
-    err |= draw_color_jitter(k, sample_ids[k], loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, value);
-  if (err) {
-    ffcv::set_error("ffcv_uniform_draw_batch_host: MT19937 stream exhausted");
-    return FFCV_EINVAL;
-  }
-  return FFCV_OK;
-}
-
 int ffcv_blur_draw_batch(void *stream, const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch,
                          double p, double sigma_lo, double sigma_hi, int ksize, uint8_t *apply, double *sigma,
                          float *weights, int32_t *status) {
   if (!blur_draw_args_ok("ffcv_blur_draw_batch", sample_ids, batch, p, sigma_lo, sigma_hi, ksize, apply, sigma,
                          weights))
     return FFCV_EINVAL;
-  if (batch == 0) return FFCV_OK;
-  hipLaunchKernelGGL(blur_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream), sample_ids,
-                     batch, loader_seed, epoch, p, sigma_lo, sigma_hi, ksize, apply, sigma, weights, status);
-  FFCV_LAUNCH_CHECK("blur_draw_kernel");
-  return FFCV_OK;
+  return ffcv::launch_draw("blur_draw_kernel", blur_draw_kernel, stream, batch, sample_ids, batch, loader_seed, epoch,
+                           p, sigma_lo, sigma_hi, ksize, apply, sigma, weights, status);
 }
 
 int ffcv_blur_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch, double p,
@@ -420,14 +367,9 @@ int ffcv_blur_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t lo
   if (!blur_draw_args_ok("ffcv_blur_draw_batch_host", sample_ids, batch, p, sigma_lo, sigma_hi, ksize, apply, sigma,
                          weights))
     return FFCV_EINVAL;
-  int err = 0;
-  for (int k = 0; k < batch; k++)
-    err |= draw_blur(k, sample_ids[k], loader_seed, epoch, p, sigma_lo, sigma_hi, ksize, apply, sigma, weights);
-  if (err) {
-    ffcv::set_error("ffcv_blur_draw_batch_host: MT19937 stream exhausted");
-    return FFCV_EINVAL;
-  }
-  return FFCV_OK;
+  return ffcv::host_draw("ffcv_blur_draw_batch_host", batch, [&](int k) {
+    return draw_blur(k, sample_ids[k], loader_seed, epoch, p, sigma_lo, sigma_hi, ksize, apply, sigma, weights);
+  });
 }
 
 uint64_t ffcv_gaussian_blur_lds_bytes(void) { return BLUR_LDS_BYTES; }

@@ -1,7 +1,8 @@
 // ffcv_color.hip -- RandomBrightness / RandomContrast / RandomSaturation
 // (color_jitter.py) as one-launch device colour jitter, with the host twin;
 // RandomGrayscale and RandomSolarization are two more steps
-// of the same launch.
+// of the same launch.  The uniform draw (ffcv_uniform_draw_batch: grayscale,
+// solarization, blur's gate) is the colour steps' draw and lives here too.
 //
 // One kernel serves both regimes.  A workgroup stages a run of whole pixels
 // of one image in LDS (the whole image when it fits CJ_LDS_BYTES, else a tile
@@ -21,23 +22,27 @@
 // LDS budget: 16 KiB of pixels + 32 B staging slack + a 256 B table: under
 // 20 KiB, so eight 256-thread workgroups (all 32 waves of a CU) fit the
 // 160 KiB of a CU and LDS never limits occupancy.  A 32x32 image is 3 KiB.
+#include <cmath>
+
 #include "api_internal.h"
 #include "color_common.h"
+#include "lds_stage.h"
 
 #define CJ_THREADS 256
 #define CJ_LDS_BYTES 16384
 #define CJ_TILE_PX 4096  // 12 KiB of pixels per workgroup beyond the whole-image regime
 enum { CJ_WHOLE = 0, CJ_SUM = 1, CJ_POINT = 2 };
 
-__global__ void __launch_bounds__(64) color_jitter_draw_kernel(const uint64_t *__restrict__ ids, int B,
-                                                               uint64_t loader_seed, uint64_t epoch, uint32_t op_id,
-                                                               double p, double lo, double hi,
-                                                               uint8_t *__restrict__ apply,
-                                                               double *__restrict__ ratio,
-                                                               int32_t *__restrict__ status) {
-  int k = blockIdx.x * blockDim.x + threadIdx.x;
+// apply[k] with probability p and value[k] uniform in [lo, hi): the draw of the
+// colour jitter steps (op ids 5-7) and of ffcv_uniform_draw_batch (9-11)
+__global__ void __launch_bounds__(64) uniform_draw_kernel(const uint64_t *__restrict__ ids, int B,
+                                                          uint64_t loader_seed, uint64_t epoch, uint32_t op_id,
+                                                          double p, double lo, double hi,
+                                                          uint8_t *__restrict__ apply, double *__restrict__ value,
+                                                          int32_t *__restrict__ status) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= B) return;
-  const int err = draw_color_jitter(k, ids[k], loader_seed, epoch, op_id, p, lo, hi, apply, ratio);
+  const int err = draw_color_jitter(k, ids[k], loader_seed, epoch, op_id, p, lo, hi, apply, value);
   if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
 }
 
@@ -49,8 +54,7 @@ __global__ void __launch_bounds__(CJ_THREADS)
     color_jitter_kernel(uint8_t *__restrict__ images, int B, uint64_t img, uint64_t npx, uint32_t prog, int s0, int s1,
                         const uint8_t *__restrict__ apply, const double *__restrict__ ratio,
                         unsigned long long *__restrict__ ws, int mode, uint32_t tile_px, uint32_t ntiles) {
-  typedef uint32_t cx4_t __attribute__((ext_vector_type(4)));
-  __shared__ cx4_t s_img[CJ_LDS_BYTES / 16 + 2];  // + the range's lead bytes and the pixel read-ahead
+  __shared__ lds_x4_t s_img[CJ_LDS_BYTES / 16 + 2];
   __shared__ uint8_t s_tab[256];
   __shared__ uint32_t s_part[CJ_THREADS / 64];
   const int t = threadIdx.x;
@@ -62,30 +66,12 @@ __global__ void __launch_bounds__(CJ_THREADS)
   const bool add_sum = mode == CJ_SUM && apply[(uint64_t)s1 * B + k] != 0;
   if (!any && !add_sum) return;  // an image no step touches is neither read nor written
 
-  // ---- stage pixels [tile * tile_px, ...) of image k: one contiguous byte
-  // range, copied with 16-byte aligned loads whatever its byte offset (an
-  // aligned chunk holding a byte of the range never crosses a page)
-  const uint64_t b0 = (uint64_t)tile * tile_px * 3u;
-  const uint32_t nbytes = (uint32_t)(img - b0 < (uint64_t)tile_px * 3u ? img - b0 : (uint64_t)tile_px * 3u);
-  const uint32_t npix = nbytes / 3u;
-  uint8_t *src = images + (uint64_t)k * img + b0;
-  const uint32_t lead = (uint32_t)((uintptr_t)src & 15);
-  typedef __attribute__((address_space(1))) cx4_t gx4_t;
-  gx4_t *gp = (gx4_t *)((uintptr_t)src & ~(uintptr_t)15);
-  const int nch = (int)((lead + nbytes + 15) >> 4);  // <= CJ_LDS_BYTES / 16 + 1
-  for (int i = t; i < nch; i += CJ_THREADS) s_img[i] = gp[i];
+  const PixelRun<CJ_THREADS> run(images, img, k, tile, tile_px, s_img);  // staging: lds_stage.h
+  run.stage(t);
   __syncthreads();
-  uint8_t *s_bytes = (uint8_t *)s_img + lead;  // byte 0 of the staged pixels
-  uint32_t *s_words = (uint32_t *)s_img;
-
-  // pixel q's R | G << 8 | B << 16 from two ALIGNED 4-byte LDS reads joined by
-  // v_alignbyte (misaligned LDS reads are several times slower); reads up to
-  // 7 bytes past the pixel's first, inside s_img
-  auto pixel = [&](uint32_t q) -> uint32_t {
-    const uint8_t *a = s_bytes + 3u * q;
-    const uint32_t *qa = (const uint32_t *)__builtin_align_down(a, 4);
-    return __builtin_amdgcn_alignbyte(qa[1], qa[0], (uint32_t)(a - (const uint8_t *)qa)) & 0xffffffu;
-  };
+  uint8_t *s_bytes = run.bytes();
+  const uint32_t npix = run.npix();
+  auto pixel = [&](uint32_t q) -> uint32_t { return lds_pixel(s_bytes + 3u * q) & 0xffffffu; };
   // the staged pixels' gray sum (fits 32 bits: <= 5461 * 254), in every thread
   auto gray_sum = [&]() -> uint32_t {
     uint32_t s = 0;
@@ -130,13 +116,10 @@ __global__ void __launch_bounds__(CJ_THREADS)
     s_tab[t] = (uint8_t)(st == FFCV_CJ_SOLARIZE ? cj_solarize(r, (uint32_t)t)
                                                 : cj_blend(r, omr, (uint32_t)t, other));  // CJ_THREADS == 256
     __syncthreads();
-    // whole words covering the staged bytes (the bytes around them are not written back)
-    const uint32_t w1 = (lead + nbytes + 3) >> 2;
-    for (uint32_t w = (lead >> 2) + t; w < w1; w += CJ_THREADS) {
-      const uint32_t v = s_words[w];
-      s_words[w] = (uint32_t)s_tab[v & 0xffu] | ((uint32_t)s_tab[(v >> 8) & 0xffu] << 8) |
-                   ((uint32_t)s_tab[(v >> 16) & 0xffu] << 16) | ((uint32_t)s_tab[v >> 24] << 24);
-    }
+    run.map_words(t, [&](uint32_t v) -> uint32_t {
+      return (uint32_t)s_tab[v & 0xffu] | ((uint32_t)s_tab[(v >> 8) & 0xffu] << 8) |
+             ((uint32_t)s_tab[(v >> 16) & 0xffu] << 16) | ((uint32_t)s_tab[v >> 24] << 24);
+    });
     __syncthreads();
   }
 
@@ -144,21 +127,7 @@ __global__ void __launch_bounds__(CJ_THREADS)
     const uint32_t total = gray_sum();
     if (t == 0) atomicAdd(&ws[k], (unsigned long long)total);
   }
-  if (!any) return;
-
-  // ---- write back: whole 16-byte chunks inside the range as one store, the
-  // two cut by its ends byte by byte (their other bytes belong to a neighbour)
-  for (int i = t; i < nch; i += CJ_THREADS) {
-    const uint32_t c0 = 16u * (uint32_t)i;
-    if (c0 >= lead && c0 + 16u <= lead + nbytes) {
-      gp[i] = s_img[i];
-    } else {
-      const uint8_t *sb = (const uint8_t *)s_img;
-      uint8_t *gb = (uint8_t *)((uintptr_t)src & ~(uintptr_t)15);
-      for (uint32_t j = c0; j < c0 + 16u; j++)
-        if (j >= lead && j < lead + nbytes) gb[j] = sb[j];
-    }
-  }
+  if (any) run.write_back(t);
 }
 
 static int cj_check_program(const char *who, const ffcv_color_jitter_params *p, int *contrast_at) {
@@ -194,6 +163,16 @@ static int cj_check_draw(const char *who, const void *ids, int batch, int op_id,
   return FFCV_OK;
 }
 
+static bool uniform_args_ok(const char *who, const void *ids, int batch, int op_id, double p, double lo, double hi,
+                            const void *apply, const void *value) {
+  if (batch < 0 || !ids || !apply || !value || op_id < 9 || op_id > 11 || !(p >= 0.0 && p <= 1.0) ||
+      !std::isfinite(lo) || !std::isfinite(hi) || !(lo <= hi)) {
+    ffcv::set_error("%s: invalid arguments (op_id %d, p %g, range %g .. %g)", who, op_id, p, lo, hi);
+    return false;
+  }
+  return true;
+}
+
 // color_jitter.py:41: uniform(max(0, 1 - magnitude), 1 + magnitude)
 static void cj_range(double magnitude, double *lo, double *hi) {
   const double l = 1.0 - magnitude;
@@ -209,13 +188,10 @@ int ffcv_color_jitter_draw_batch(void *stream, const uint64_t *sample_ids, int b
                                  double *ratio, int32_t *status) {
   if (cj_check_draw("ffcv_color_jitter_draw_batch", sample_ids, batch, op_id, p, magnitude, apply, ratio))
     return FFCV_EINVAL;
-  if (batch == 0) return FFCV_OK;
   double lo, hi;
   cj_range(magnitude, &lo, &hi);
-  hipLaunchKernelGGL(color_jitter_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream),
-                     sample_ids, batch, loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, ratio, status);
-  FFCV_LAUNCH_CHECK("color_jitter_draw_kernel");
-  return FFCV_OK;
+  return ffcv::launch_draw("uniform_draw_kernel", uniform_draw_kernel, stream, batch, sample_ids, batch, loader_seed,
+                           epoch, (uint32_t)op_id, p, lo, hi, apply, ratio, status);
 }
 
 int ffcv_color_jitter_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch,
@@ -224,14 +200,27 @@ int ffcv_color_jitter_draw_batch_host(const uint64_t *sample_ids, int batch, uin
     return FFCV_EINVAL;
   double lo, hi;
   cj_range(magnitude, &lo, &hi);
-  int err = 0;
-  for (int k = 0; k < batch; k++)
-    err |= draw_color_jitter(k, sample_ids[k], loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, ratio);
-  if (err) {
-    ffcv::set_error("ffcv_color_jitter_draw_batch_host: MT19937 stream exhausted");
+  return ffcv::host_draw("ffcv_color_jitter_draw_batch_host", batch, [&](int k) {
+    return draw_color_jitter(k, sample_ids[k], loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, ratio);
+  });
+}
+
+int ffcv_uniform_draw_batch(void *stream, const uint64_t *sample_ids, int batch, uint64_t loader_seed,
+                            uint64_t epoch, int op_id, double p, double lo, double hi, uint8_t *apply,
+                            double *value, int32_t *status) {
+  if (!uniform_args_ok("ffcv_uniform_draw_batch", sample_ids, batch, op_id, p, lo, hi, apply, value))
     return FFCV_EINVAL;
-  }
-  return FFCV_OK;
+  return ffcv::launch_draw("uniform_draw_kernel", uniform_draw_kernel, stream, batch, sample_ids, batch, loader_seed,
+                           epoch, (uint32_t)op_id, p, lo, hi, apply, value, status);
+}
+
+int ffcv_uniform_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch,
+                                 int op_id, double p, double lo, double hi, uint8_t *apply, double *value) {
+  if (!uniform_args_ok("ffcv_uniform_draw_batch_host", sample_ids, batch, op_id, p, lo, hi, apply, value))
+    return FFCV_EINVAL;
+  return ffcv::host_draw("ffcv_uniform_draw_batch_host", batch, [&](int k) {
+    return draw_color_jitter(k, sample_ids[k], loader_seed, epoch, (uint32_t)op_id, p, lo, hi, apply, value);
+  });
 }
 
 uint64_t ffcv_color_jitter_workspace_bytes(int batch) { return batch > 0 ? 8ull * (uint64_t)batch : 0; }
@@ -240,11 +229,8 @@ uint64_t ffcv_color_jitter_lds_bytes(void) { return CJ_LDS_BYTES; }
 int ffcv_color_jitter_batch(void *stream, uint8_t *images, int batch, int height, int width,
                             const ffcv_color_jitter_params *params, const uint8_t *apply, const double *ratio,
                             void *workspace, uint64_t workspace_bytes) {
-  if (batch < 0 || !images || !params || !apply || !ratio || height <= 0 || width <= 0 ||
-      (uint64_t)height * width * 3 > 0x7fffffffull) {
-    ffcv::set_error("ffcv_color_jitter_batch: invalid arguments");
+  if (!ffcv::u8_images_ok("ffcv_color_jitter_batch", images && params && apply && ratio, batch, height, width))
     return FFCV_EINVAL;
-  }
   int c = -1;
   if (cj_check_program("ffcv_color_jitter_batch", params, &c)) return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
@@ -253,18 +239,15 @@ int ffcv_color_jitter_batch(void *stream, uint8_t *images, int batch, int height
       (uint32_t)params->steps[0] | ((uint32_t)params->steps[1] << 8) | ((uint32_t)params->steps[2] << 16);
   const uint64_t npx = (uint64_t)height * width, img = npx * 3;
   const bool whole = img <= CJ_LDS_BYTES;
-  const uint32_t tile_px = whole ? (uint32_t)npx : CJ_TILE_PX;
-  const uint64_t ntiles = (npx + tile_px - 1) / tile_px;
-  const uint64_t blocks = (uint64_t)batch * ntiles;
-  if (blocks > 0x7fffffffull) {
-    ffcv::set_error("ffcv_color_jitter_batch: %llu workgroups exceed one launch", (unsigned long long)blocks);
+  uint32_t tile_px, ntiles;
+  unsigned blocks;
+  if (!ffcv::run_tiling("ffcv_color_jitter_batch", batch, npx, CJ_LDS_BYTES, CJ_TILE_PX, &tile_px, &ntiles, &blocks))
     return FFCV_EINVAL;
-  }
   hipStream_t s = ffcv::as_stream(stream);
   unsigned long long *ws = (unsigned long long *)workspace;
   if (whole || c < 0) {
-    hipLaunchKernelGGL(color_jitter_kernel, dim3((unsigned)blocks), dim3(CJ_THREADS), 0, s, images, batch, img, npx,
-                       prog, 0, n, apply, ratio, ws, whole ? CJ_WHOLE : CJ_POINT, tile_px, (uint32_t)ntiles);
+    hipLaunchKernelGGL(color_jitter_kernel, dim3(blocks), dim3(CJ_THREADS), 0, s, images, batch, img, npx, prog, 0, n,
+                       apply, ratio, ws, whole ? CJ_WHOLE : CJ_POINT, tile_px, ntiles);
     FFCV_LAUNCH_CHECK("color_jitter_kernel");
     return FFCV_OK;
   }
@@ -276,21 +259,19 @@ int ffcv_color_jitter_batch(void *stream, uint8_t *images, int batch, int height
     return FFCV_EINVAL;
   }
   FFCV_HIP_CHECK(hipMemsetAsync(workspace, 0, 8ull * (uint64_t)batch, s));
-  hipLaunchKernelGGL(color_jitter_kernel, dim3((unsigned)blocks), dim3(CJ_THREADS), 0, s, images, batch, img, npx,
-                     prog, 0, c, apply, ratio, ws, CJ_SUM, tile_px, (uint32_t)ntiles);
+  hipLaunchKernelGGL(color_jitter_kernel, dim3(blocks), dim3(CJ_THREADS), 0, s, images, batch, img, npx, prog, 0, c,
+                     apply, ratio, ws, CJ_SUM, tile_px, ntiles);
   FFCV_LAUNCH_CHECK("color_jitter_kernel (pass A)");
-  hipLaunchKernelGGL(color_jitter_kernel, dim3((unsigned)blocks), dim3(CJ_THREADS), 0, s, images, batch, img, npx,
-                     prog, c, n, apply, ratio, ws, CJ_POINT, tile_px, (uint32_t)ntiles);
+  hipLaunchKernelGGL(color_jitter_kernel, dim3(blocks), dim3(CJ_THREADS), 0, s, images, batch, img, npx, prog, c, n,
+                     apply, ratio, ws, CJ_POINT, tile_px, ntiles);
   FFCV_LAUNCH_CHECK("color_jitter_kernel (pass B)");
   return FFCV_OK;
 }
 
 int ffcv_color_jitter_batch_host(uint8_t *images, int batch, int height, int width,
                                  const ffcv_color_jitter_params *params, const uint8_t *apply, const double *ratio) {
-  if (batch < 0 || !images || !params || !apply || !ratio || height <= 0 || width <= 0) {
-    ffcv::set_error("ffcv_color_jitter_batch_host: invalid arguments");
+  if (!ffcv::u8_images_ok("ffcv_color_jitter_batch_host", images && params && apply && ratio, batch, height, width))
     return FFCV_EINVAL;
-  }
   int c = -1;
   if (cj_check_program("ffcv_color_jitter_batch_host", params, &c)) return FFCV_EINVAL;
   const uint64_t npx = (uint64_t)height * width;

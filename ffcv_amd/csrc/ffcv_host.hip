@@ -218,13 +218,8 @@ int ffcv_translate_draw_batch_host(const uint64_t *sample_ids, int batch, uint64
     ffcv::set_error("ffcv_translate_draw_batch_host: invalid arguments (padding %d)", padding);
     return FFCV_EINVAL;
   }
-  int err = 0;
-  for (int k = 0; k < batch; k++) err |= draw_translate(k, sample_ids[k], loader_seed, epoch, padding, yx);
-  if (err) {
-    ffcv::set_error("ffcv_translate_draw_batch_host: MT19937 stream exhausted");
-    return FFCV_EINVAL;
-  }
-  return FFCV_OK;
+  return ffcv::host_draw("ffcv_translate_draw_batch_host", batch,
+                         [&](int k) { return draw_translate(k, sample_ids[k], loader_seed, epoch, padding, yx); });
 }
 
 int ffcv_imdecode_device(unsigned char *input_buffer, uint64_t input_size, uint32_t source_height,

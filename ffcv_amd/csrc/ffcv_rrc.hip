@@ -1095,11 +1095,8 @@ int ffcv_translate_draw_batch(void *stream, const uint64_t *sample_ids, int batc
     ffcv::set_error("ffcv_translate_draw_batch: invalid arguments (padding %d)", padding);
     return FFCV_EINVAL;
   }
-  if (batch == 0) return FFCV_OK;
-  hipLaunchKernelGGL(translate_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream),
-                     sample_ids, batch, loader_seed, epoch, padding, yx, status);
-  FFCV_LAUNCH_CHECK("translate_draw_kernel");
-  return FFCV_OK;
+  return ffcv::launch_draw("translate_draw_kernel", translate_draw_kernel, stream, batch, sample_ids, batch,
+                           loader_seed, epoch, padding, yx, status);
 }
 
 int ffcv_translate_batch(void *stream, const uint8_t *in, uint8_t *out, int batch, int height, int width,

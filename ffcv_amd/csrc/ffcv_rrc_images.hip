@@ -18,6 +18,7 @@
 
 #include "api_internal.h"
 #include "device_common.h"
+#include "lds_stage.h"
 
 #define RRCI_THREADS 256
 // The largest staged source (rows of whole 16-byte chunks, see lds_src_bytes)
@@ -92,25 +93,19 @@ FFCV_HD bool crop_ok(int i, int j, int h, int w, int H, int W) {
 
 // 16-byte chunks of one LDS row: the aligned chunks that can hold bytes of a
 // crop row of w pixels at any alignment
-FFCV_HD int row_chunks(int w) { return (3 * w + 30) >> 4; }
+FFCV_HD int row_chunks(int w) { return lds_chunks(3 * w); }
 // LDS bytes of the staged source of an H x W image (any crop of it), plus the
 // pixel reads' look-ahead (two aligned dwords per pixel: up to 5 bytes past it)
 static uint64_t lds_src_bytes(int H, int W) { return (uint64_t)H * row_chunks(W) * 16 + 16; }
 
 // Crop rows in LDS: row y holds the 16-byte aligned chunks covering crop row
-// y, so its first byte sits at the row's alignment offset.  A pixel's three
-// bytes come from two ALIGNED 4-byte LDS reads joined by v_alignbyte (adjacent
-// byte reads are merged into misaligned reads, several times slower).
+// y, so its first byte sits at the row's alignment offset (lds_stage.h).
 struct ImgLds {
   const uint8_t *p;
   int pitch, lead, stepmod;
   FFCV_DEV const uint8_t *row(int y) const { return p + y * pitch + ((lead + y * stepmod) & 15); }
   FFCV_DEV const uint8_t *pix(int y, int x) const { return row(y) + x * 3; }
-  FFCV_DEV uint32_t px(int y, int x) const {
-    const uint8_t *q = pix(y, x);
-    const uint32_t *qa = (const uint32_t *)__builtin_align_down(q, 4);
-    return __builtin_amdgcn_alignbyte(qa[1], qa[0], (uint32_t)(q - (const uint8_t *)qa));
-  }
+  FFCV_DEV uint32_t px(int y, int x) const { return lds_pixel(pix(y, x)); }
   FFCV_DEV int at(int y, int x, int c) const { return (int)((px(y, x) >> (8 * c)) & 0xffu); }
 };
 
@@ -442,12 +437,9 @@ int ffcv_crop_draw_batch(void *stream, const uint64_t *sample_ids, int batch, in
     ffcv::set_error("ffcv_crop_draw_batch: invalid arguments");
     return FFCV_EINVAL;
   }
-  if (batch == 0) return FFCV_OK;
   const CropRanges rg{{scale[0], scale[1]}, {ratio[0], ratio[1]}};
-  hipLaunchKernelGGL(crop_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream), sample_ids,
-                     batch, (uint32_t)height, (uint32_t)width, rg, loader_seed, epoch, crops, status);
-  FFCV_LAUNCH_CHECK("crop_draw_kernel");
-  return FFCV_OK;
+  return ffcv::launch_draw("crop_draw_kernel", crop_draw_kernel, stream, batch, sample_ids, batch, (uint32_t)height,
+                           (uint32_t)width, rg, loader_seed, epoch, crops, status);
 }
 
 int ffcv_crop_draw_batch_host(const uint64_t *sample_ids, int batch, int height, int width, const double scale[2],

@@ -86,10 +86,10 @@ __global__ void __launch_bounds__(TONE_THREADS)
     __syncthreads();
   }
 
-  // ---- stage pixels [tile * tile_px, ...) of image k: one contiguous byte
-  // range, copied with 16-byte aligned loads whatever its byte offset (an
-  // aligned chunk holding a byte of the range never crosses a page), and
-  // counted from the registers on the way
+  // ---- stage pixels [tile * tile_px, ...) of image k, counted from the
+  // registers on the way.  This is PixelRun's scheme (lds_stage.h) written out:
+  // on the helper this kernel measured slower at 512 x 32 x 32
+  // (profiles/lds_stage_ab.txt).
   const uint64_t b0 = (uint64_t)tile * tile_px * 3u;
   const uint32_t nbytes = (uint32_t)(img - b0 < (uint64_t)tile_px * 3u ? img - b0 : (uint64_t)tile_px * 3u);
   uint8_t *src = images + (uint64_t)k * img + b0;
@@ -297,24 +297,16 @@ int ffcv_tone_draw_batch(void *stream, const uint64_t *sample_ids, int batch, ui
                          int n, const int32_t *op_ids, const double *p, uint8_t *apply, int32_t *status) {
   ToneDraw d;
   if (tone_check_draw("ffcv_tone_draw_batch", sample_ids, batch, n, op_ids, p, apply, &d)) return FFCV_EINVAL;
-  if (batch == 0) return FFCV_OK;
-  hipLaunchKernelGGL(tone_draw_kernel, dim3((batch + 63) / 64), dim3(64), 0, ffcv::as_stream(stream), sample_ids,
-                     batch, loader_seed, epoch, d, apply, status);
-  FFCV_LAUNCH_CHECK("tone_draw_kernel");
-  return FFCV_OK;
+  return ffcv::launch_draw("tone_draw_kernel", tone_draw_kernel, stream, batch, sample_ids, batch, loader_seed, epoch,
+                           d, apply, status);
 }
 
 int ffcv_tone_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t loader_seed, uint64_t epoch, int n,
                               const int32_t *op_ids, const double *p, uint8_t *apply) {
   ToneDraw d;
   if (tone_check_draw("ffcv_tone_draw_batch_host", sample_ids, batch, n, op_ids, p, apply, &d)) return FFCV_EINVAL;
-  int err = 0;
-  for (int k = 0; k < batch; k++) err |= draw_tone(k, batch, sample_ids[k], loader_seed, epoch, d, apply);
-  if (err) {
-    ffcv::set_error("ffcv_tone_draw_batch_host: MT19937 stream exhausted");
-    return FFCV_EINVAL;
-  }
-  return FFCV_OK;
+  return ffcv::host_draw("ffcv_tone_draw_batch_host", batch,
+                         [&](int k) { return draw_tone(k, batch, sample_ids[k], loader_seed, epoch, d, apply); });
 }
 
 uint64_t ffcv_tone_workspace_bytes(int batch) { return batch > 0 ? 3072ull * (uint64_t)batch : 0; }
@@ -322,11 +314,7 @@ uint64_t ffcv_tone_lds_bytes(void) { return TONE_LDS_BYTES; }
 
 int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height, int width, const ffcv_tone_params *params,
                     const uint8_t *apply, void *workspace, uint64_t workspace_bytes) {
-  if (batch < 0 || !images || !params || !apply || height <= 0 || width <= 0 ||
-      (uint64_t)height * width * 3 > 0x7fffffffull) {
-    ffcv::set_error("ffcv_tone_batch: invalid arguments (batch %d, %dx%d)", batch, height, width);
-    return FFCV_EINVAL;
-  }
+  if (!ffcv::u8_images_ok("ffcv_tone_batch", images && params && apply, batch, height, width)) return FFCV_EINVAL;
   bool stats = false;
   if (tone_check_program("ffcv_tone_batch", params, &stats)) return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
@@ -335,19 +323,15 @@ int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height, int wi
   for (int i = 0; i < n; i++) prog |= (uint32_t)params->steps[i] << (8 * i);
   const uint64_t npx = (uint64_t)height * width, img = npx * 3;
   const bool whole = img <= TONE_LDS_BYTES;
-  const uint32_t tile_px = whole ? (uint32_t)npx : TONE_TILE_PX;
-  const uint64_t ntiles = (npx + tile_px - 1) / tile_px;
-  const uint64_t blocks = (uint64_t)batch * ntiles;
-  if (blocks > 0x7fffffffull) {
-    ffcv::set_error("ffcv_tone_batch: %llu workgroups exceed one launch", (unsigned long long)blocks);
+  uint32_t tile_px, ntiles;
+  unsigned blocks;
+  if (!ffcv::run_tiling("ffcv_tone_batch", batch, npx, TONE_LDS_BYTES, TONE_TILE_PX, &tile_px, &ntiles, &blocks))
     return FFCV_EINVAL;
-  }
   hipStream_t s = ffcv::as_stream(stream);
   uint32_t *ws = (uint32_t *)workspace;
   if (whole || !stats) {
-    hipLaunchKernelGGL(tone_kernel, dim3((unsigned)blocks), dim3(TONE_THREADS), 0, s, images, batch, img,
-                       (uint32_t)npx, prog, n, (int)params->bits, apply, ws, whole ? TONE_WHOLE : TONE_MAP, tile_px,
-                       (uint32_t)ntiles);
+    hipLaunchKernelGGL(tone_kernel, dim3(blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx, prog, n,
+                       (int)params->bits, apply, ws, whole ? TONE_WHOLE : TONE_MAP, tile_px, ntiles);
     FFCV_LAUNCH_CHECK("tone_kernel");
     return FFCV_OK;
   }
@@ -359,22 +343,19 @@ int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height, int wi
     return FFCV_EINVAL;
   }
   FFCV_HIP_CHECK(hipMemsetAsync(workspace, 0, ffcv_tone_workspace_bytes(batch), s));
-  hipLaunchKernelGGL(tone_kernel, dim3((unsigned)blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx,
-                     prog, n, (int)params->bits, apply, ws, TONE_HIST, tile_px, (uint32_t)ntiles);
+  hipLaunchKernelGGL(tone_kernel, dim3(blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx, prog, n,
+                     (int)params->bits, apply, ws, TONE_HIST, tile_px, ntiles);
   FFCV_LAUNCH_CHECK("tone_kernel (pass A)");
-  hipLaunchKernelGGL(tone_kernel, dim3((unsigned)blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx,
-                     prog, n, (int)params->bits, apply, ws, TONE_MAP, tile_px, (uint32_t)ntiles);
+  hipLaunchKernelGGL(tone_kernel, dim3(blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx, prog, n,
+                     (int)params->bits, apply, ws, TONE_MAP, tile_px, ntiles);
   FFCV_LAUNCH_CHECK("tone_kernel (pass B)");
   return FFCV_OK;
 }
 
 int ffcv_tone_batch_host(uint8_t *images, int batch, int height, int width, const ffcv_tone_params *params,
                          const uint8_t *apply) {
-  if (batch < 0 || !images || !params || !apply || height <= 0 || width <= 0 ||
-      (uint64_t)height * width * 3 > 0x7fffffffull) {
-    ffcv::set_error("ffcv_tone_batch_host: invalid arguments (batch %d, %dx%d)", batch, height, width);
+  if (!ffcv::u8_images_ok("ffcv_tone_batch_host", images && params && apply, batch, height, width))
     return FFCV_EINVAL;
-  }
   bool stats = false;
   if (tone_check_program("ffcv_tone_batch_host", params, &stats)) return FFCV_EINVAL;
   const uint64_t npx = (uint64_t)height * width;

@@ -533,10 +533,29 @@ def flip_batch(inp, out, flips, stream=None):
            'ffcv_flip_batch')
 
 
+def _seed64(loader_seed):
+    """The loader's seed as the uint64 the C ABI takes."""
+    return int(loader_seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _u8_batch_dims(images, who):
+    """(B, H, W) of a contiguous uint8 (B, H, W, 3) batch: a numpy array for a
+    ``*_host`` entry, else a tensor."""
+    if who.endswith('_host'):
+        ok = isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.flags.c_contiguous
+        what = 'C-contiguous uint8 (B, H, W, 3) array'
+    else:
+        ok = not isinstance(images, np.ndarray) and images.element_size() == 1 and images.is_contiguous()
+        what = 'contiguous uint8 (B, H, W, 3) tensor'
+    if not ok or len(images.shape) != 4 or int(images.shape[3]) != 3:
+        raise TypeError(f'{who}: a {what} is required')
+    return int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+
+
 def translate_draw_batch(ids, loader_seed, epoch, padding, yx, status=None, stream=None):
     """RandomTranslate windows (y, x) of the batch on the device (op id 4)."""
     _check(lib().ffcv_translate_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                           int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(padding),
+                                           _seed64(loader_seed), int(epoch), int(padding),
                                            _p(yx), _p(status)), 'ffcv_translate_draw_batch')
 
 
@@ -544,7 +563,7 @@ def translate_draw_batch_host(ids, loader_seed, epoch, padding):
     """The same draws on the host: int32 (B, 2) of (y, x)."""
     ids = np.ascontiguousarray(ids, dtype=np.uint64)
     yx = np.empty((ids.size, 2), np.int32)
-    _check(lib().ffcv_translate_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+    _check(lib().ffcv_translate_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed),
                                                 int(epoch), int(padding), _p(yx)),
            'ffcv_translate_draw_batch_host')
     return yx
@@ -566,7 +585,7 @@ def crop_draw_batch(ids, height, width, scale, ratio, loader_seed, epoch, crops,
     device (op id 8): ids device int64 / uint64 [B], crops device int32 (B, 4)."""
     sc, ra = _ranges(scale, ratio)
     _check(lib().ffcv_crop_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]), int(height), int(width), sc, ra,
-                                      int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), _p(crops), _p(status)),
+                                      _seed64(loader_seed), int(epoch), _p(crops), _p(status)),
            'ffcv_crop_draw_batch')
 
 
@@ -576,7 +595,7 @@ def crop_draw_batch_host(ids, height, width, scale, ratio, loader_seed, epoch, s
     crops = np.empty((ids.size, 4), np.int32)
     sc, ra = _ranges(scale, ratio)
     _check(lib().ffcv_crop_draw_batch_host(_p(ids), int(ids.size), int(height), int(width), sc, ra,
-                                           int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), _p(crops), _p(status)),
+                                           _seed64(loader_seed), int(epoch), _p(crops), _p(status)),
            'ffcv_crop_draw_batch_host')
     return crops
 
@@ -661,7 +680,7 @@ def color_jitter_draw_batch(ids, loader_seed, epoch, op_id, p, magnitude, apply,
     """Colour-jitter decisions of the batch on the device: apply uint8[B],
     ratio float64[B] (op id 5 brightness, 6 contrast, 7 saturation)."""
     _check(lib().ffcv_color_jitter_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                              int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(op_id),
+                                              _seed64(loader_seed), int(epoch), int(op_id),
                                               float(p), float(magnitude), _p(apply), _p(ratio), _p(status)),
            'ffcv_color_jitter_draw_batch')
 
@@ -671,7 +690,7 @@ def color_jitter_draw_batch_host(ids, loader_seed, epoch, op_id, p, magnitude):
     ids = np.ascontiguousarray(ids, dtype=np.uint64)
     apply = np.empty(ids.size, np.uint8)
     ratio = np.empty(ids.size, np.float64)
-    _check(lib().ffcv_color_jitter_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+    _check(lib().ffcv_color_jitter_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed),
                                                    int(epoch), int(op_id), float(p), float(magnitude), _p(apply),
                                                    _p(ratio)), 'ffcv_color_jitter_draw_batch_host')
     return apply, ratio
@@ -689,9 +708,7 @@ def color_jitter_batch(images, steps, apply, ratio, workspace=None, stream=None)
     """The program ``steps`` in place on a device uint8 (B, H, W, 3) batch
     (apply uint8 (n, B), ratio float64 (n, B)); one launch while an image fits
     color_jitter_lds_bytes(), else one without and two with a contrast step."""
-    if images.dim() != 4 or int(images.shape[3]) != 3 or images.element_size() != 1 or not images.is_contiguous():
-        raise TypeError('color_jitter_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
-    B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    B, H, W = _u8_batch_dims(images, 'color_jitter_batch')
     params = steps if isinstance(steps, ColorJitterParams) else color_jitter_params(steps)
     wb = int(workspace.numel() * workspace.element_size()) if workspace is not None else 0
     _check(lib().ffcv_color_jitter_batch(_stream(stream), _p(images), B, H, W, ctypes.byref(params), _p(apply),
@@ -700,10 +717,7 @@ def color_jitter_batch(images, steps, apply, ratio, workspace=None, stream=None)
 
 def color_jitter_batch_host(images, steps, apply, ratio):
     """The same program in place on a C-contiguous numpy uint8 (B, H, W, 3)."""
-    if not (isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.flags.c_contiguous
-            and images.ndim == 4 and images.shape[3] == 3):
-        raise TypeError('color_jitter_batch_host: a C-contiguous uint8 (B, H, W, 3) array is required')
-    B, H, W = (int(x) for x in images.shape[:3])
+    B, H, W = _u8_batch_dims(images, 'color_jitter_batch_host')
     params = steps if isinstance(steps, ColorJitterParams) else color_jitter_params(steps)
     apply = np.ascontiguousarray(apply, np.uint8).reshape(params.n_steps, B)
     ratio = np.ascontiguousarray(ratio, np.float64).reshape(params.n_steps, B)
@@ -716,7 +730,7 @@ def uniform_draw_batch(ids, loader_seed, epoch, op_id, p, lo, hi, apply, value, 
     """``rand() < p`` then ``uniform(lo, hi)`` of the batch on the device (op id
     9 grayscale, 10 solarization, 11 blur): apply uint8[B], value float64[B]."""
     _check(lib().ffcv_uniform_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                         int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(op_id), float(p),
+                                         _seed64(loader_seed), int(epoch), int(op_id), float(p),
                                          float(lo), float(hi), _p(apply), _p(value), _p(status)),
            'ffcv_uniform_draw_batch')
 
@@ -726,7 +740,7 @@ def uniform_draw_batch_host(ids, loader_seed, epoch, op_id, p, lo, hi):
     ids = np.ascontiguousarray(ids, dtype=np.uint64)
     apply = np.empty(ids.size, np.uint8)
     value = np.empty(ids.size, np.float64)
-    _check(lib().ffcv_uniform_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+    _check(lib().ffcv_uniform_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed),
                                               int(epoch), int(op_id), float(p), float(lo), float(hi), _p(apply),
                                               _p(value)), 'ffcv_uniform_draw_batch_host')
     return apply, value
@@ -740,7 +754,7 @@ def blur_draw_batch(ids, loader_seed, epoch, p, sigma_lo, sigma_hi, ksize, apply
     """GaussianBlur's draws of the batch on the device (op id 11): apply
     uint8[B], sigma float64[B], weights float32 (B, 32)."""
     _check(lib().ffcv_blur_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                      int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p), float(sigma_lo),
+                                      _seed64(loader_seed), int(epoch), float(p), float(sigma_lo),
                                       float(sigma_hi), int(ksize), _p(apply), _p(sigma), _p(weights), _p(status)),
            'ffcv_blur_draw_batch')
 
@@ -752,7 +766,7 @@ def blur_draw_batch_host(ids, loader_seed, epoch, p, sigma_lo, sigma_hi, ksize):
     apply = np.empty(ids.size, np.uint8)
     sigma = np.empty(ids.size, np.float64)
     weights = np.empty((ids.size, BLUR_WROW), np.float32)
-    _check(lib().ffcv_blur_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch),
+    _check(lib().ffcv_blur_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch),
                                            float(p), float(sigma_lo), float(sigma_hi), int(ksize), _p(apply),
                                            _p(sigma), _p(weights)), 'ffcv_blur_draw_batch_host')
     return apply, sigma, weights
@@ -807,7 +821,7 @@ def hue_draw_batch(ids, loader_seed, epoch, p, magnitude, apply, shift, status=N
     """RandomHue's decisions of the batch on the device (op id 12): apply
     uint8[B], shift float64[B] = uniform(-magnitude, magnitude)."""
     _check(lib().ffcv_hue_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                     int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p), float(magnitude),
+                                     _seed64(loader_seed), int(epoch), float(p), float(magnitude),
                                      _p(apply), _p(shift), _p(status)), 'ffcv_hue_draw_batch')
 
 
@@ -816,7 +830,7 @@ def hue_draw_batch_host(ids, loader_seed, epoch, p, magnitude):
     ids = np.ascontiguousarray(ids, dtype=np.uint64)
     apply = np.empty(ids.size, np.uint8)
     shift = np.empty(ids.size, np.float64)
-    _check(lib().ffcv_hue_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch),
+    _check(lib().ffcv_hue_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch),
                                           float(p), float(magnitude), _p(apply), _p(shift)),
            'ffcv_hue_draw_batch_host')
     return apply, shift
@@ -840,7 +854,7 @@ def color_jitter_joint_draw_batch(ids, loader_seed, epoch, p, magnitude, apply, 
     (brightness, contrast, saturation, hue) with a non-zero magnitude."""
     m = _magnitude4(magnitude)
     _check(lib().ffcv_color_jitter_joint_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                                    int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p),
+                                                    _seed64(loader_seed), int(epoch), float(p),
                                                     _p(m), _p(apply), _p(ratio), _p(status)),
            'ffcv_color_jitter_joint_draw_batch')
 
@@ -853,7 +867,7 @@ def color_jitter_joint_draw_batch_host(ids, loader_seed, epoch, p, magnitude):
     apply = np.empty((max(rows, 1), ids.size), np.uint8)
     ratio = np.empty((max(rows, 1), ids.size), np.float64)
     _check(lib().ffcv_color_jitter_joint_draw_batch_host(_p(ids), int(ids.size),
-                                                         int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p),
+                                                         _seed64(loader_seed), int(epoch), float(p),
                                                          _p(m), _p(apply), _p(ratio)),
            'ffcv_color_jitter_joint_draw_batch_host')
     return apply[:rows], ratio[:rows]
@@ -863,19 +877,14 @@ def hue_batch(images, apply, shift, stream=None):
     """The hue shift in place on a device uint8 (B, H, W, 3) batch, one launch:
     image k turns by shift[k] where apply[k] != 0 (apply uint8 (B,), shift
     float64 (B,), both on the device)."""
-    if images.dim() != 4 or int(images.shape[3]) != 3 or images.element_size() != 1 or not images.is_contiguous():
-        raise TypeError('hue_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
-    B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    B, H, W = _u8_batch_dims(images, 'hue_batch')
     _check(lib().ffcv_hue_batch(_stream(stream), _p(images), B, H, W, _p(apply), _p(shift)), 'ffcv_hue_batch')
     return images
 
 
 def hue_batch_host(images, apply, shift):
     """The same in place on a C-contiguous numpy uint8 (B, H, W, 3)."""
-    if not (isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.flags.c_contiguous
-            and images.ndim == 4 and images.shape[3] == 3):
-        raise TypeError('hue_batch_host: a C-contiguous uint8 (B, H, W, 3) array is required')
-    B, H, W = (int(x) for x in images.shape[:3])
+    B, H, W = _u8_batch_dims(images, 'hue_batch_host')
     apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
     shift = np.ascontiguousarray(shift, np.float64).reshape(-1)
     if apply.size != B or shift.size != B:
@@ -912,7 +921,7 @@ def tone_draw_batch(ids, loader_seed, epoch, op_ids, ps, apply, status=None, str
     apply uint8 (n, B), row i ``rand() < ps[i]`` from the stream of op_ids[i]."""
     ops, ps = _tone_pairs(op_ids, ps)
     _check(lib().ffcv_tone_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                      int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(ops.size), _p(ops),
+                                      _seed64(loader_seed), int(epoch), int(ops.size), _p(ops),
                                       _p(ps), _p(apply), _p(status)), 'ffcv_tone_draw_batch')
 
 
@@ -921,7 +930,7 @@ def tone_draw_batch_host(ids, loader_seed, epoch, op_ids, ps):
     ids = np.ascontiguousarray(ids, dtype=np.uint64)
     ops, ps = _tone_pairs(op_ids, ps)
     apply = np.empty((max(int(ops.size), 1), ids.size), np.uint8)
-    _check(lib().ffcv_tone_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch),
+    _check(lib().ffcv_tone_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch),
                                            int(ops.size), _p(ops), _p(ps), _p(apply)), 'ffcv_tone_draw_batch_host')
     return apply
 
@@ -938,9 +947,7 @@ def tone_batch(images, steps, bits, apply, workspace=None, stream=None):
     """The program ``steps`` in place on a device uint8 (B, H, W, 3) batch
     (apply uint8 (n, B)); one launch while an image fits tone_lds_bytes(), else
     one without and two with an autocontrast or equalize step."""
-    if images.dim() != 4 or int(images.shape[3]) != 3 or images.element_size() != 1 or not images.is_contiguous():
-        raise TypeError('tone_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
-    B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    B, H, W = _u8_batch_dims(images, 'tone_batch')
     params = steps if isinstance(steps, ToneParams) else tone_params(steps, bits)
     wb = int(workspace.numel() * workspace.element_size()) if workspace is not None else 0
     _check(lib().ffcv_tone_batch(_stream(stream), _p(images), B, H, W, ctypes.byref(params), _p(apply),
@@ -949,10 +956,7 @@ def tone_batch(images, steps, bits, apply, workspace=None, stream=None):
 
 def tone_batch_host(images, steps, bits, apply):
     """The same program in place on a C-contiguous numpy uint8 (B, H, W, 3)."""
-    if not (isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.flags.c_contiguous
-            and images.ndim == 4 and images.shape[3] == 3):
-        raise TypeError('tone_batch_host: a C-contiguous uint8 (B, H, W, 3) array is required')
-    B, H, W = (int(x) for x in images.shape[:3])
+    B, H, W = _u8_batch_dims(images, 'tone_batch_host')
     params = steps if isinstance(steps, ToneParams) else tone_params(steps, bits)
     apply = np.ascontiguousarray(apply, np.uint8).reshape(max(params.n_steps, 1), B)
     _check(lib().ffcv_tone_batch_host(_p(images), B, H, W, ctypes.byref(params), _p(apply)), 'ffcv_tone_batch_host')
@@ -992,7 +996,7 @@ def affine_draw_batch(ids, loader_seed, epoch, p, ranges, height, width, apply, 
     the device (op id 14): apply uint8[B], coef int64 (B, 6)."""
     r = _ranges12(ranges)
     _check(lib().ffcv_affine_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
-                                        int(loader_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), float(p), _p(r),
+                                        _seed64(loader_seed), int(epoch), float(p), _p(r),
                                         int(height), int(width), _p(apply), _p(coef), _p(status)),
            'ffcv_affine_draw_batch')
 
@@ -1003,7 +1007,7 @@ def affine_draw_batch_host(ids, loader_seed, epoch, p, ranges, height, width):
     r = _ranges12(ranges)
     apply = np.empty(ids.size, np.uint8)
     coef = np.empty((ids.size, 6), np.int64)
-    _check(lib().ffcv_affine_draw_batch_host(_p(ids), int(ids.size), int(loader_seed) & 0xFFFFFFFFFFFFFFFF,
+    _check(lib().ffcv_affine_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed),
                                              int(epoch), float(p), _p(r), int(height), int(width), _p(apply),
                                              _p(coef)), 'ffcv_affine_draw_batch_host')
     return apply, coef

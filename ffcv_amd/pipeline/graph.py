@@ -15,9 +15,9 @@ stages and generates stage functions with ``ast``.  Here:
    RandomTranslate (with RandomHorizontalFlip / Cutout in any order, then
    NormalizeImage(float16)) is lowered the same way into the small-image
    launch (``_lower_simple``).  A run of adjacent colour-jitter operations
-   (grayscale and solarization included) becomes one launch of its own
-   (``_lower_color``), and so does a run of adjacent table operations
-   (posterize, autocontrast, equalize, invert: ``_lower_tone``).  A
+   (grayscale and solarization included) becomes one launch of its own, and
+   so does a run of adjacent table operations (posterize, autocontrast,
+   equalize, invert): ``_lower_runs``.  A
    RandomResizedCrop transform on device data absorbs the Cutout / RandomHorizontalFlip /
    NormalizeImage(float16) behind it (``_lower_rrc_transform``).
 3. ``collect_requirements`` walks states exactly like graph.py:295-354.  A
@@ -156,9 +156,11 @@ class Graph:
         from ..fields.rgb_image import ResizedCropRGBImageDecoder, SimpleRGBImageDecoder
         if self.device.type != 'cuda':
             return
+        from ..transforms.color_jitter import _ColorJitter
+        from ..transforms.tone import _Tone
         for chain in self._chains.values():
-            self._lower_color(chain)
-            self._lower_tone(chain)
+            self._lower_runs(chain, _ColorJitter, 3)
+            self._lower_runs(chain, _Tone, 4)
         for name, chain in self._chains.items():
             if chain and type(chain[0]) is SimpleRGBImageDecoder:
                 self._lower_simple(chain)
@@ -278,40 +280,23 @@ class Graph:
             op._absorbed = True
         dec.fuse(steps=steps, normalize=norm)
 
-    def _lower_color(self, chain):
-        """A run of adjacent RandomBrightness / RandomContrast /
-        RandomSaturation / RandomGrayscale / RandomSolarization, each kind at
-        most once and at most three in all: ONE device launch behind the
-        draws (ffcv_color_jitter_batch).  The first operation of the run
-        carries the program, the others run as identities; a repeated kind,
-        or a fourth operation, starts a new run.  (To the decoder lowerings a colour-jitter
-        operation is an unknown operation: it ends the fused prefix.)"""
-        from ..transforms.color_jitter import _ColorJitter
+    def _lower_runs(self, chain, base_class, max_len):
+        """A run of adjacent operations of one family, each type at most once
+        and at most max_len in all, is ONE device launch behind its draws:
+        the first operation of the run carries the program, the others run as
+        identities; a repeated type, or one operation more, starts a new run.
+        The families: RandomBrightness / RandomContrast / RandomSaturation /
+        RandomGrayscale / RandomSolarization (three to a launch of
+        ffcv_color_jitter_batch) and RandomPosterize / RandomAutocontrast /
+        RandomEqualize / RandomInvert (one draw launch and one
+        ffcv_tone_batch).  (To the decoder lowerings such an operation is an
+        unknown operation: it ends the fused prefix.)"""
         run = []
         for op in chain:
-            if not isinstance(op, _ColorJitter) or len(self.operation_to_node[op]) != 1:
+            if not isinstance(op, base_class) or len(self.operation_to_node[op]) != 1:
                 run = []
                 continue
-            if len(run) == 3 or any(type(o) is type(op) for o in run):
-                run = []
-            run.append(op)
-            if len(run) > 1:
-                op._absorbed = True
-                run[0]._program = list(run)
-
-    def _lower_tone(self, chain):
-        """A run of adjacent RandomPosterize / RandomAutocontrast /
-        RandomEqualize / RandomInvert, each type at most once (so at most
-        four): ONE draw launch and ONE ffcv_tone_batch.  The first operation
-        of the run carries the program, the others run as identities; a
-        repeated type starts a new run."""
-        from ..transforms.tone import _Tone
-        run = []
-        for op in chain:
-            if not isinstance(op, _Tone) or len(self.operation_to_node[op]) != 1:
-                run = []
-                continue
-            if len(run) == 4 or any(type(o) is type(op) for o in run):
+            if len(run) == max_len or any(type(o) is type(op) for o in run):
                 run = []
             run.append(op)
             if len(run) > 1:

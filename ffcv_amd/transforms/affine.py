@@ -18,16 +18,15 @@ arrays it is the host twins over the Loader's threads.
 """
 import math
 import numbers
-from dataclasses import replace
 from typing import Callable, Optional, Tuple
 
 import numpy as np
 import torch as ch
 
 from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
+from .u8_image import _U8ImageOp
 
 _MODES = {'bilinear': 0, 'nearest': 1}       # FFCV_AFFINE_*
 
@@ -46,7 +45,7 @@ def _is_number(x):
     return isinstance(x, numbers.Real) and not isinstance(x, bool)
 
 
-class RandomAffine(Operation):
+class RandomAffine(_U8ImageOp):
     """Randomly rotate, translate, scale and shear the image about its centre.
     Operates on raw arrays (not tensors).
 
@@ -70,8 +69,6 @@ class RandomAffine(Operation):
     p : float
         probability to warp
     """
-    device_aware = True
-    per_sample = True
     op_id = 14
     _name = 'RandomAffine'
 
@@ -119,13 +116,7 @@ class RandomAffine(Operation):
         if not ok:
             raise ValueError(f'{name}: fill must be a number or an RGB triple, got {fill!r}')
         self.fill = f
-        try:
-            pf = float(p)
-        except (TypeError, ValueError):
-            raise ValueError(f'{name}: p must be a number, got {p!r}')
-        if not 0 <= pf <= 1:
-            raise ValueError(f'{name}: p must lie in [0, 1], got {p!r}')
-        self.p = p
+        self.p = self.check_p(name, p)
 
     def fill_u8(self):
         return np.broadcast_to(np.asarray(self.fill).astype(np.uint8).reshape(-1), (3,)).copy()
@@ -171,17 +162,10 @@ class RandomAffine(Operation):
         return affine
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
-        dt, shape = previous_state.dtype, previous_state.shape
-        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
-        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
-            raise TypeError(f'{self._name} works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
-                            'place it before ToTorchImage / NormalizeImage / Convert')
+        _, shape = self.check_u8_images(previous_state)
         if max(shape[0], shape[1]) > 32767:
             raise TypeError(f'{self._name}: images of {shape[0]}x{shape[1]} exceed the supported 32767 per side')
-        if previous_state.device.type == 'cuda':
-            return (replace(previous_state, jit_mode=False),
-                    AllocationQuery(tuple(shape), dt, previous_state.device))
-        return (replace(previous_state, jit_mode=not isinstance(dt, ch.dtype)), AllocationQuery(tuple(shape), dt))
+        return self.declare_out_of_place(previous_state)
 
 
 class RandomRotation(RandomAffine):

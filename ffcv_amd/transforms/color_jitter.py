@@ -21,17 +21,14 @@ first operation of the run carry the program); on host arrays each operation
 runs the numpy statement below, in place.
 """
 import math
-from dataclasses import replace
-from typing import Callable, Optional, Tuple
+from typing import Callable
 
 import numpy as np
 import torch as ch
 
-from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
-from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
+from .u8_image import _U8ImageOp
 
 _IDENT = np.arange(256, dtype=np.float64)
 
@@ -88,9 +85,7 @@ def jitter_draw(seed, epoch, sample, op_id, p, magnitude):
     return apply, np.float64(rs.uniform(lo, hi))
 
 
-class _ColorJitter(Operation):
-    device_aware = True
-    per_sample = True
+class _ColorJitter(_U8ImageOp):
     op_id = 0      # seeding-contract op id
     kind = 0       # FFCV_CJ_*
     host_fn = None
@@ -99,17 +94,13 @@ class _ColorJitter(Operation):
         super().__init__()
         name = type(self).__name__
         try:
-            m, pf = float(magnitude), float(p)
+            m = float(magnitude)
         except (TypeError, ValueError):
-            raise ValueError(f'{name}: magnitude and p must be numbers, got {magnitude!r}, {p!r}')
+            raise ValueError(f'{name}: magnitude must be a number, got {magnitude!r}')
         if not math.isfinite(m) or m < 0:
             raise ValueError(f'{name}: magnitude must be finite and >= 0, got {magnitude!r}')
-        if not 0 <= pf <= 1:
-            raise ValueError(f'{name}: p must lie in [0, 1], got {p!r}')
         self.magnitude = magnitude
-        self.p = p
-        self._absorbed = False
-        self._program = [self]  # the run this operation leads (graph lowering)
+        self.p = self.check_p(name, p)
 
     def draw_device(self, ctx, apply, ratio):
         """The batch's decisions into device apply uint8[B] / ratio float64[B]."""
@@ -122,9 +113,7 @@ class _ColorJitter(Operation):
 
     def generate_code(self) -> Callable:
         if self._absorbed:
-            def fused(images, *_):
-                return images
-            return fused
+            return self.identity()
         program = list(self._program)
 
         def color_jitter(images, dst, indices):
@@ -153,15 +142,6 @@ class _ColorJitter(Operation):
         color_jitter.is_parallel = True
         color_jitter.with_indices = True
         return color_jitter
-
-    def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
-        dt, shape = previous_state.dtype, previous_state.shape
-        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
-        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
-            raise TypeError(f'{type(self).__name__} works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
-                            'place it before ToTorchImage / NormalizeImage / Convert')
-        return replace(previous_state, jit_mode=previous_state.device.type == 'cpu'
-                       and not isinstance(dt, ch.dtype)), None
 
 
 class RandomBrightness(_ColorJitter):
@@ -218,16 +198,8 @@ class _UniformDraw(_ColorJitter):
     lo = hi = 0.0
 
     def __init__(self, p):
-        Operation.__init__(self)
-        try:
-            pf = float(p)
-        except (TypeError, ValueError):
-            raise ValueError(f'{type(self).__name__}: p must be a number, got {p!r}')
-        if not 0 <= pf <= 1:
-            raise ValueError(f'{type(self).__name__}: p must lie in [0, 1], got {p!r}')
-        self.p = p
-        self._absorbed = False
-        self._program = [self]
+        _U8ImageOp.__init__(self)
+        self.p = self.check_p(type(self).__name__, p)
 
     def draw_device(self, ctx, apply, ratio):
         from .. import libffcv as L

@@ -15,19 +15,18 @@ same launch.  On host arrays it is the host twins over the Loader's threads.
 """
 import math
 import numbers
-from dataclasses import replace
 from typing import Callable, Optional, Tuple
 
 import numpy as np
 import torch as ch
 
 from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
+from .u8_image import _U8ImageOp
 
 
-class GaussianBlur(Operation):
+class GaussianBlur(_U8ImageOp):
     """Randomly blur the image with a Gaussian kernel of random sigma.
     Operates on raw arrays (not tensors).
 
@@ -40,8 +39,6 @@ class GaussianBlur(Operation):
     p : float
         probability to blur
     """
-    device_aware = True
-    per_sample = True
     op_id = 11
 
     def __init__(self, kernel_size: int, sigma=(0.1, 2.0), p=0.5):
@@ -51,17 +48,13 @@ class GaussianBlur(Operation):
             raise ValueError(f'GaussianBlur: kernel_size must be an odd int in [1, 31], got {kernel_size!r}')
         try:
             lo, hi = (float(sigma),) * 2 if isinstance(sigma, numbers.Real) else (float(x) for x in sigma)
-            pf = float(p)
         except (TypeError, ValueError):
-            raise ValueError(f'GaussianBlur: sigma must be a number or a (low, high) pair and p a number, got '
-                             f'{sigma!r}, {p!r}')
+            raise ValueError(f'GaussianBlur: sigma must be a number or a (low, high) pair, got {sigma!r}')
         if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi):
             raise ValueError(f'GaussianBlur: sigma must be finite with 0 < low <= high, got {sigma!r}')
-        if not 0 <= pf <= 1:
-            raise ValueError(f'GaussianBlur: p must lie in [0, 1], got {p!r}')
         self.kernel_size = int(kernel_size)
         self.sigma = (lo, hi)
-        self.p = p
+        self.p = self.check_p('GaussianBlur', p)
 
     def generate_code(self) -> Callable:
         from .. import libffcv as L
@@ -98,15 +91,8 @@ class GaussianBlur(Operation):
         return gaussian_blur
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
-        dt, shape = previous_state.dtype, previous_state.shape
-        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
-        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
-            raise TypeError(f'GaussianBlur works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
-                            'place it before ToTorchImage / NormalizeImage / Convert')
+        _, shape = self.check_u8_images(previous_state)
         if (self.kernel_size - 1) // 2 >= min(shape[0], shape[1]):
             raise TypeError(f'GaussianBlur: kernel_size {self.kernel_size} reflects past a {shape[0]}x{shape[1]} '
                             'image ((kernel_size - 1) / 2 must be below its height and width)')
-        if previous_state.device.type == 'cuda':
-            return (replace(previous_state, jit_mode=False),
-                    AllocationQuery(tuple(shape), dt, previous_state.device))
-        return (replace(previous_state, jit_mode=not isinstance(dt, ch.dtype)), AllocationQuery(tuple(shape), dt))
+        return self.declare_out_of_place(previous_state)

@@ -27,18 +27,15 @@ ffcv_hue_batch; a stage no component needs is left out.  On host arrays each
 sample runs the numpy statements, in place.
 """
 import math
-from dataclasses import replace
-from typing import Callable, Optional, Tuple
+from typing import Callable
 
 import numpy as np
 import torch as ch
 
-from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
-from ..pipeline.state import State
 from ..pipeline import runtime
 from .color_jitter import brightness_np, contrast_np, saturation_np, jitter_range
 from .rng import contract_seed
+from .u8_image import _U8ImageOp
 
 OP_HUE, OP_JOINT = 12, 13
 _F32 = np.float32
@@ -105,11 +102,6 @@ def _number(cls, name, value):
         raise ValueError(f'{cls}: {name} must be a number, got {value!r}')
 
 
-def _check_p(cls, p):
-    if not 0 <= _number(cls, 'p', p) <= 1:
-        raise ValueError(f'{cls}: p must lie in [0, 1], got {p!r}')
-
-
 def _check_hue(cls, name, value):
     m = _number(cls, name, value)
     if not (math.isfinite(m) and 0 <= m <= 0.5):
@@ -117,21 +109,7 @@ def _check_hue(cls, name, value):
     return m
 
 
-class _HueBase(Operation):
-    device_aware = True
-    per_sample = True
-
-    def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
-        dt, shape = previous_state.dtype, previous_state.shape
-        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
-        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
-            raise TypeError(f'{type(self).__name__} works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
-                            'place it before ToTorchImage / NormalizeImage / Convert')
-        return replace(previous_state, jit_mode=previous_state.device.type == 'cpu'
-                       and not isinstance(dt, ch.dtype)), None
-
-
-class RandomHue(_HueBase):
+class RandomHue(_U8ImageOp):
     """Randomly turn the image's hue. Operates on raw arrays (not tensors).
 
     Parameters
@@ -147,9 +125,8 @@ class RandomHue(_HueBase):
     def __init__(self, magnitude: float, p=0.5):
         super().__init__()
         _check_hue('RandomHue', 'magnitude', magnitude)
-        _check_p('RandomHue', p)
         self.magnitude = magnitude
-        self.p = p
+        self.p = self.check_p('RandomHue', p)
 
     def generate_code(self) -> Callable:
         p, magnitude = float(self.p), float(self.magnitude)
@@ -178,7 +155,7 @@ class RandomHue(_HueBase):
         return random_hue
 
 
-class RandomColorJitter(_HueBase):
+class RandomColorJitter(_U8ImageOp):
     """Randomly jitter brightness, contrast, saturation and hue under ONE
     decision, in that order. Operates on raw arrays (not tensors).
 
@@ -201,9 +178,8 @@ class RandomColorJitter(_HueBase):
             if not math.isfinite(m) or m < 0:
                 raise ValueError(f'RandomColorJitter: {name} must be finite and >= 0, got {v!r}')
         _check_hue('RandomColorJitter', 'hue', hue)
-        _check_p('RandomColorJitter', p)
         self.brightness, self.contrast, self.saturation, self.hue = brightness, contrast, saturation, hue
-        self.p = p
+        self.p = self.check_p('RandomColorJitter', p)
 
     @property
     def magnitudes(self):

@@ -17,17 +17,14 @@ carry the program); on host arrays each operation runs the numpy statement, in
 place.
 """
 import numbers
-from dataclasses import replace
-from typing import Callable, Optional, Tuple
+from typing import Callable
 
 import numpy as np
 import torch as ch
 
-from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
-from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
+from .u8_image import _U8ImageOp
 
 OP_POSTERIZE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_INVERT = 15, 16, 17, 18
 _IDENT = np.arange(256, dtype=np.uint8)
@@ -98,9 +95,7 @@ def tone_draw(seed, epoch, sample, op_id, p):
     return bool(np.random.RandomState(contract_seed(seed, epoch, int(sample), op_id)).rand() < p)
 
 
-class _Tone(Operation):
-    device_aware = True
-    per_sample = True
+class _Tone(_U8ImageOp):
     op_id = 0      # seeding-contract op id
     kind = 0       # FFCV_TONE_*
     bits = 8       # posterize's parameter
@@ -108,21 +103,11 @@ class _Tone(Operation):
 
     def __init__(self, p):
         super().__init__()
-        try:
-            pf = float(p)
-        except (TypeError, ValueError):
-            raise ValueError(f'{type(self).__name__}: p must be a number, got {p!r}')
-        if not 0 <= pf <= 1:
-            raise ValueError(f'{type(self).__name__}: p must lie in [0, 1], got {p!r}')
-        self.p = p
-        self._absorbed = False
-        self._program = [self]  # the run this operation leads (graph lowering)
+        self.p = self.check_p(type(self).__name__, p)
 
     def generate_code(self) -> Callable:
         if self._absorbed:
-            def fused(images, *_):
-                return images
-            return fused
+            return self.identity()
         program = list(self._program)
         kinds, op_ids, ps = [op.kind for op in program], [op.op_id for op in program], [float(op.p) for op in program]
         bits = next((op.bits for op in program if op.kind == 1), 8)
@@ -151,15 +136,6 @@ class _Tone(Operation):
         tone.is_parallel = True
         tone.with_indices = True
         return tone
-
-    def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
-        dt, shape = previous_state.dtype, previous_state.shape
-        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
-        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
-            raise TypeError(f'{type(self).__name__} works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
-                            'place it before ToTorchImage / NormalizeImage / Convert')
-        return replace(previous_state, jit_mode=previous_state.device.type == 'cpu'
-                       and not isinstance(dt, ch.dtype)), None
 
 
 class RandomPosterize(_Tone):

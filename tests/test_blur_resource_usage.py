@@ -5,7 +5,6 @@ flags (no GPU needed).
 Every kernel of the file must run without scratch and without VGPR or SGPR
 spills.  As written the compiler reports, for gfx950:
 
-  uniform_draw_kernel   (one lane per sample)            9 VGPRs, 8 waves/SIMD
   blur_draw_kernel      (one lane per sample, k exps)   42 VGPRs, 8 waves/SIMD
   gaussian_blur_kernel  (a workgroup per tile)          62 VGPRs, 8 waves/SIMD
 
@@ -27,7 +26,6 @@ CSRC = os.path.join(ROOT, 'ffcv_amd', 'csrc')
 
 # kernel name fragment -> (VGPRs, waves/SIMD)
 BUDGET = {
-    'uniform_draw_kernel': (9, 8),
     'blur_draw_kernel': (42, 8),
     'gaussian_blur_kernel': (62, 8),
 }
