@@ -997,6 +997,14 @@ int ffcv_rrc_raw_batch(void *stream, const uint8_t *base, const ffcv_sample *sam
   return ffcv_rrc_raw_batch_ws(stream, base, samples, batch, crops, cutout_yx, flips, p, out, nullptr, 0);
 }
 
+// gather_raw_kernel, flip_kernel and translate_kernel take the image from
+// blockIdx.y, and a grid has at most 65,535 rows: their entries launch a larger
+// batch in slices of that many images, with the per-image pointers advanced.
+#define MAX_GRID_Y 65535
+static inline unsigned slice_of(int batch, int64_t k0) {
+  return (unsigned)(batch - k0 < MAX_GRID_Y ? batch - k0 : MAX_GRID_Y);
+}
+
 int ffcv_gather_samples(void *stream, const ffcv_sample *table, uint64_t n_table, const uint64_t *ids,
                         int batch, ffcv_sample *out) {
   if (!table || !ids || !out || batch < 0) {
@@ -1019,9 +1027,11 @@ int ffcv_gather_raw_batch(void *stream, const uint8_t *base, const ffcv_sample *
   if (batch == 0) return FFCV_OK;
   unsigned gx = (unsigned)((out_stride + 255) / 256);
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(gather_raw_kernel, dim3(gx, batch), dim3(256), 0, ffcv::as_stream(stream), base,
-                     samples, out, out_stride);
-  FFCV_LAUNCH_CHECK("gather_raw_kernel");
+  for (int64_t k0 = 0; k0 < batch; k0 += MAX_GRID_Y) {
+    hipLaunchKernelGGL(gather_raw_kernel, dim3(gx, slice_of(batch, k0)), dim3(256), 0, ffcv::as_stream(stream),
+                       base, samples + k0, out + out_stride * k0, out_stride);
+    FFCV_LAUNCH_CHECK("gather_raw_kernel");
+  }
   return FFCV_OK;
 }
 
@@ -1083,9 +1093,11 @@ int ffcv_flip_batch(void *stream, const uint8_t *in, uint8_t *out, int batch, in
   uint64_t img = (uint64_t)height * width * channels_bytes;
   unsigned gx = (unsigned)((img + 255) / 256);
   if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(flip_kernel, dim3(gx, batch), dim3(256), 0, ffcv::as_stream(stream), in, out, height,
-                     width, channels_bytes, flips);
-  FFCV_LAUNCH_CHECK("flip_kernel");
+  for (int64_t k0 = 0; k0 < batch; k0 += MAX_GRID_Y) {
+    hipLaunchKernelGGL(flip_kernel, dim3(gx, slice_of(batch, k0)), dim3(256), 0, ffcv::as_stream(stream),
+                       in + img * k0, out + img * k0, height, width, channels_bytes, flips + k0);
+    FFCV_LAUNCH_CHECK("flip_kernel");
+  }
   return FFCV_OK;
 }
 
@@ -1110,9 +1122,12 @@ int ffcv_translate_batch(void *stream, const uint8_t *in, uint8_t *out, int batc
   uint64_t img = (uint64_t)height * width * 3;
   unsigned gx = (unsigned)((img + 255) / 256);
   if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(translate_kernel, dim3(gx, batch), dim3(256), 0, ffcv::as_stream(stream), in, out, height,
-                     width, yx, padding, fill[0], fill[1], fill[2]);
-  FFCV_LAUNCH_CHECK("translate_kernel");
+  for (int64_t k0 = 0; k0 < batch; k0 += MAX_GRID_Y) {
+    hipLaunchKernelGGL(translate_kernel, dim3(gx, slice_of(batch, k0)), dim3(256), 0, ffcv::as_stream(stream),
+                       in + img * k0, out + img * k0, height, width, yx + 2 * (uint64_t)k0, padding, fill[0], fill[1],
+                       fill[2]);
+    FFCV_LAUNCH_CHECK("translate_kernel");
+  }
   return FFCV_OK;
 }
 

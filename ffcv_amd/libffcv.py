@@ -507,8 +507,28 @@ def gather_rows(base, base_bytes, row_off, ids, row_bytes, out, out_stride, stat
     _check(fn(*args, int(shape)), 'ffcv_gather_rows_shape')
 
 
+def _dense_device(who, *tensors, what='tensor'):
+    """Every tensor is contiguous, and every one is in device memory (what the
+    standalone kernels index); the layout is checked first."""
+    for t in tensors:
+        if isinstance(t, np.ndarray) or not hasattr(t, 'data_ptr') or not t.is_contiguous():
+            raise TypeError(f'{who}: a contiguous device {what} is required')
+    for t in tensors:
+        if not t.is_cuda:
+            raise TypeError(f'{who}: the {what} must be in device memory, got one on {t.device}')
+
+
+def _u8_device_dims(images, who):
+    """_u8_batch_dims of a tensor that is in device memory."""
+    dims = _u8_batch_dims(images, who)
+    _dense_device(who, images)
+    return dims
+
+
 def cutout_batch(images, yx, crop_size, fill, stream=None):
-    B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    """cutout.py:36-47 in place on a contiguous device uint8 (B, H, W, 3) batch;
+    yx device int32 (B, 2), every origin >= 0."""
+    B, H, W = _u8_device_dims(images, 'cutout_batch')
     f = (ctypes.c_uint8 * 3)(*[int(x) for x in fill])
     _check(lib().ffcv_cutout_batch(_stream(stream), _p(images), B, H, W, _p(yx), int(crop_size),
                                    f), 'ffcv_cutout_batch')
@@ -521,14 +541,26 @@ def normalize_batch(inp, lut, out, stream=None):
 
 def lut_batch(inp, lut, out, stream=None):
     """out[i] = lut[inp[i]*3 + i%3] for a [256,3] device table of any dtype
-    (element size 1/2/4/8)."""
+    (element size 1/2/4/8); inp: contiguous device uint8 whose last dimension
+    is the channel, out: contiguous, of the table's element size."""
+    _dense_device('lut_batch', inp, lut, out)
+    if inp.element_size() != 1 or int(lut.numel()) != 768 or out.element_size() != lut.element_size() or \
+            out.numel() < inp.numel():
+        raise TypeError('lut_batch: a uint8 input, a (256, 3) table and an output of the table\'s element size '
+                        'with room for every input element are required')
     _check(lib().ffcv_lut_batch(_stream(stream), _p(inp), int(inp.numel()), _p(lut),
                                 int(lut.element_size()), _p(out)), 'ffcv_lut_batch')
 
 
 def flip_batch(inp, out, flips, stream=None):
+    """flip.py:35-40 of a contiguous device (B, H, W, ...) batch of any element
+    size into ``out`` (same shape and element size, not ``inp``)."""
+    _dense_device('flip_batch', inp, out, what='(B, H, W, ...) tensor')
+    if inp.dim() < 3 or tuple(out.shape) != tuple(inp.shape) or out.element_size() != inp.element_size():
+        raise TypeError('flip_batch: contiguous device (B, H, W, ...) tensors of one shape and element size are '
+                        f'required, got {tuple(inp.shape)} and {tuple(out.shape)}')
     B, H, W = int(inp.shape[0]), int(inp.shape[1]), int(inp.shape[2])
-    cb = int(inp[0, 0, 0].numel() * inp.element_size())
+    cb = int(np.prod([int(x) for x in inp.shape[3:]], dtype=np.int64)) * int(inp.element_size())
     _check(lib().ffcv_flip_batch(_stream(stream), _p(inp), _p(out), B, H, W, cb, _p(flips)),
            'ffcv_flip_batch')
 
@@ -570,7 +602,13 @@ def translate_draw_batch_host(ids, loader_seed, epoch, padding):
 
 
 def translate_batch(inp, out, yx, padding, fill, stream=None):
-    B, H, W = int(inp.shape[0]), int(inp.shape[1]), int(inp.shape[2])
+    """translate.py:35-44 of a contiguous device uint8 (B, H, W, 3) batch into
+    ``out`` (same shape, not ``inp``); yx device int32 (B, 2)."""
+    B, H, W = _u8_batch_dims(inp, 'translate_batch')
+    if _u8_batch_dims(out, 'translate_batch') != (B, H, W):
+        raise TypeError(f'translate_batch: out must have the input\'s shape {tuple(inp.shape)}, got '
+                        f'{tuple(out.shape)}')
+    _dense_device('translate_batch', inp, out)
     f = (ctypes.c_uint8 * 3)(*[int(x) for x in fill])
     _check(lib().ffcv_translate_batch(_stream(stream), _p(inp), _p(out), B, H, W, _p(yx), int(padding), f),
            'ffcv_translate_batch')

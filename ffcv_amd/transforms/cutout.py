@@ -5,6 +5,9 @@ RandomResizedCrop/CenterCrop decoder (the graph lowering does this);
 otherwise runs as its own device kernel, or on host numpy arrays.  The
 square origin is ``(randint(H-c+1), randint(W-c+1))`` drawn from the
 sample's own MT19937 (op id 2) under the seeding contract.
+On the device it takes uint8 (H, W, 3) images only: behind ToTorchImage,
+NormalizeImage or Convert it refuses the pipeline (the kernel would read an
+NCHW view as H = 3, W = H).
 """
 from dataclasses import replace
 from typing import Callable, Optional, Tuple
@@ -17,6 +20,7 @@ from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
+from .u8_image import check_u8_images
 
 
 class Cutout(Operation):
@@ -71,5 +75,7 @@ class Cutout(Operation):
         return cutout_square
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
+        if previous_state.device.type == 'cuda' and not self._absorbed:   # the device kernel reads (B, H, W, 3) uint8
+            check_u8_images('Cutout', previous_state)
         return replace(previous_state, jit_mode=previous_state.device.type == 'cpu'
                        and not isinstance(previous_state.dtype, ch.dtype)), None

@@ -3,7 +3,9 @@
 Flip decision per sample: one double from the sample's MT19937 (op id 3)
 ``< flip_prob`` (the reference draws ``rand(B) < flip_prob`` for the batch,
 flip.py:35).  Fused into the crop/resize kernel when it follows the
-decoder; otherwise a device kernel or host numpy.
+decoder; otherwise a device kernel or host numpy.  On the device it takes
+uint8 (H, W, 3) images only: behind ToTorchImage, NormalizeImage or Convert it
+refuses the pipeline.
 """
 from dataclasses import replace
 from typing import Callable, Optional, Tuple
@@ -16,6 +18,7 @@ from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
+from .u8_image import check_u8_images
 
 
 class RandomHorizontalFlip(Operation):
@@ -67,6 +70,8 @@ class RandomHorizontalFlip(Operation):
         if self._absorbed:
             return previous_state, None
         on_dev = previous_state.device.type == 'cuda'
+        if on_dev:   # the device kernel reads (B, H, W, 3) uint8
+            check_u8_images('RandomHorizontalFlip', previous_state)
         return (replace(previous_state, jit_mode=not on_dev and not isinstance(previous_state.dtype, ch.dtype)),
                 AllocationQuery(previous_state.shape, previous_state.dtype,
                                 previous_state.device if on_dev else None))

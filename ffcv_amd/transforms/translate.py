@@ -10,7 +10,9 @@ contract (DESIGN.md).
 Fused into the small-image kernel (ffcv_simple_aug_batch) when it follows a
 SimpleRGBImageDecoder of raw samples (the graph lowering does this);
 otherwise it runs as its own device kernel into its own buffer (shifted reads
-overlap the writes, so not in place), or on host numpy arrays.
+overlap the writes, so not in place), or on host numpy arrays.  On the device
+it takes uint8 (H, W, 3) images only: behind ToTorchImage, NormalizeImage or
+Convert it refuses the pipeline.
 """
 import numbers
 from dataclasses import replace
@@ -24,6 +26,7 @@ from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
+from .u8_image import check_u8_images
 
 
 def translate_window(image, dst, y, x, padding, fill):
@@ -98,6 +101,8 @@ class RandomTranslate(Operation):
         if self._absorbed:
             return previous_state, None
         on_dev = previous_state.device.type == 'cuda'
+        if on_dev:   # the device kernel reads (B, H, W, 3) uint8
+            check_u8_images('RandomTranslate', previous_state)
         return (replace(previous_state, jit_mode=not on_dev and not isinstance(previous_state.dtype, ch.dtype)),
                 AllocationQuery(previous_state.shape, previous_state.dtype,
                                 previous_state.device if on_dev else None))

@@ -12,6 +12,16 @@ from ..pipeline.operation import Operation
 from ..pipeline.state import State
 
 
+def check_u8_images(label, previous_state: State):
+    """(dtype, shape) of a state of uint8 (H, W, 3) images; anything else raises."""
+    dt, shape = previous_state.dtype, previous_state.shape
+    is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
+    if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
+        raise TypeError(f'{label} works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
+                        'place it before ToTorchImage / NormalizeImage / Convert')
+    return dt, shape
+
+
 class _U8ImageOp(Operation):
     device_aware = True
     per_sample = True
@@ -43,12 +53,7 @@ class _U8ImageOp(Operation):
         return fused
 
     def check_u8_images(self, previous_state: State):
-        dt, shape = previous_state.dtype, previous_state.shape
-        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
-        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
-            raise TypeError(f'{self._label} works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
-                            'place it before ToTorchImage / NormalizeImage / Convert')
-        return dt, shape
+        return check_u8_images(self._label, previous_state)
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         """In place."""

@@ -249,7 +249,10 @@ int ffcv_gather_samples(void *stream, const ffcv_sample *table, uint64_t n_table
                         const uint64_t *ids, int batch, ffcv_sample *out);
 
 /* rgb_image.py:123-136 SimpleRGBImageDecoder raw branch (my_memcpy per
- * sample) as a device gather into [B][H][W][3]. */
+ * sample) as a device gather into [B][H][W][3]: row k of `out` receives the
+ * `size` bytes of a mode-1 (raw) sample; the rest of the row, and the row of
+ * a sample of another mode, are not written.  Any batch >= 0 (more than
+ * 65,535 samples go out as several launches). */
 int ffcv_gather_raw_batch(void *stream, const uint8_t *base,
                           const ffcv_sample *samples, int batch, uint8_t *out,
                           uint64_t out_stride);
@@ -396,7 +399,9 @@ int ffcv_jpeg_coefficients_batch(ffcv_jpeg_ctx *ctx, void *stream,
                                  int32_t *status);
 
 /* ---------------------------------------------- standalone transforms -- */
-/* cutout.py:36-47 in place on a device [B][H][W][3] uint8 batch. */
+/* cutout.py:36-47 in place on a device [B][H][W][3] uint8 batch.  Each
+ * origin cutout_yx[k] = (y, x) must be >= 0 in both coordinates; the part of
+ * the square past the bottom or right edge of the image is dropped. */
 int ffcv_cutout_batch(void *stream, uint8_t *images, int batch, int height,
                       int width, const int32_t *cutout_yx, int crop_size,
                       const uint8_t fill[3]);
@@ -409,7 +414,9 @@ int ffcv_lut_batch(void *stream, const uint8_t *in, uint64_t n,
 /* ffcv_lut_batch with a fp16 (int16 bits) table (normalize.py:45-48). */
 int ffcv_normalize_batch(void *stream, const uint8_t *in, uint64_t n,
                          const uint16_t *lut, uint16_t *out);
-/* flip.py:35-40: dst[i] = images[i, :, ::-1] where flips[i] != 0. */
+/* flip.py:35-40: dst[i] = images[i, :, ::-1] where flips[i] != 0, a copy
+ * otherwise, for pixels of channels_bytes bytes (in == out is FFCV_EINVAL).
+ * Any batch >= 0 (more than 65,535 images go out as several launches). */
 int ffcv_flip_batch(void *stream, const uint8_t *in, uint8_t *out, int batch,
                     int height, int width, int channels_bytes,
                     const uint8_t *flips);
@@ -432,7 +439,8 @@ int ffcv_translate_draw_batch_host(const uint64_t *sample_ids, int batch,
                                    uint64_t loader_seed, uint64_t epoch,
                                    int padding, int32_t *yx);
 /* Standalone translate of a device [B][H][W][3] uint8 batch into `out`
- * (same shape; in == out is FFCV_EINVAL: shifted reads overlap the writes). */
+ * (same shape; in == out is FFCV_EINVAL: shifted reads overlap the writes).
+ * Any batch >= 0 (more than 65,535 images go out as several launches). */
 int ffcv_translate_batch(void *stream, const uint8_t *in, uint8_t *out,
                          int batch, int height, int width, const int32_t *yx,
                          int padding, const uint8_t fill[3]);
