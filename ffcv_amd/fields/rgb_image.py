@@ -32,6 +32,7 @@ import numpy as np
 import torch as ch
 
 from .base import Field, ARG_TYPE
+from ..pipeline.epilogue import Epilogue, FusesEpilogue
 from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline.allocation_query import AllocationQuery
@@ -81,25 +82,28 @@ def _raise_failed(L, status, ids):
                           + L.lib().ffcv_last_error().decode(errors='replace'))
 
 
-class SimpleRGBImageDecoder(Operation):
+class SimpleRGBImageDecoder(FusesEpilogue, Operation):
     """Most basic decoder for the :class:`~ffcv.fields.RGBImageField`.
 
     Constant-resolution datasets only; reads (and decompresses) images as is.
     """
     device_aware = True
     per_sample = True
+    _fused_steps = ()
 
     def __init__(self):
         super().__init__()
-        self._fused_steps = ()
-        self._fused_normalize = None
+        self._epilogue = Epilogue()
 
     # graph lowering hook: the flip / translate / cutout operations (in
     # pipeline order) and the fp16 NormalizeImage that the small-image kernel
     # (ffcv_simple_aug_batch) applies while it reads the raw samples
     def fuse(self, steps=(), normalize=None):
+        from ..transforms import Cutout, RandomHorizontalFlip
         self._fused_steps = tuple(steps)
-        self._fused_normalize = normalize if self._fused_steps else None
+        cutout, flip = (next((s for s in self._fused_steps if isinstance(s, cls)), None)
+                        for cls in (Cutout, RandomHorizontalFlip))
+        self._epilogue = Epilogue(cutout, flip, normalize=normalize if self._fused_steps else None)
 
     @property
     def fused(self):
@@ -108,7 +112,7 @@ class SimpleRGBImageDecoder(Operation):
 
     @property
     def output_dtype(self):
-        return ch.float16 if self._fused_normalize is not None else ch.uint8
+        return self._epilogue.output_dtype(ch.uint8)
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, AllocationQuery]:
         widths = self.metadata['width']
@@ -207,46 +211,35 @@ instead."""
             return out[:B]
         return decode
 
+    def _aug_params(self):
+        """(SimpleAugParams of the fused steps, the RandomTranslate among them or None)."""
+        from .. import libffcv as L
+        from ..transforms import RandomTranslate
+        ep = self._epilogue
+        ap = ep.fill_cutout(L.SimpleAugParams())
+        ap.n_steps = len(self._fused_steps)
+        tr = None
+        for i, op in enumerate(self._fused_steps):
+            if op is ep.flip:
+                ap.steps[i] = L.AUG_FLIP
+            elif op is ep.cutout:
+                ap.steps[i] = L.AUG_CUTOUT
+            elif isinstance(op, RandomTranslate):
+                ap.steps[i], tr = L.AUG_TRANSLATE, op
+                ap.padding = int(op.padding)
+                ap.translate_fill[:3] = op.fill_u8().tolist()
+            else:
+                raise TypeError(f'{type(op).__name__} cannot be fused into SimpleRGBImageDecoder')
+        return ap, tr
+
     def _generate_code_fused(self, f_ix) -> Callable:
         """Raw samples through flip / translate / cutout (+ fp16 LUT) in one
         launch behind the draws (ffcv_simple_aug_batch): each sample is read
         once from the .beton bytes and its final pixels are written once."""
         from .. import libffcv as L
-        from ..transforms import Cutout, RandomHorizontalFlip, RandomTranslate
-        ap = L.SimpleAugParams()
-        ap.n_steps = len(self._fused_steps)
-        flip = cut = tr = None
-        for i, op in enumerate(self._fused_steps):
-            if isinstance(op, RandomHorizontalFlip):
-                ap.steps[i], flip = L.AUG_FLIP, op
-            elif isinstance(op, RandomTranslate):
-                ap.steps[i], tr = L.AUG_TRANSLATE, op
-                ap.padding = int(op.padding)
-                for c, v in enumerate(op.fill_u8()):
-                    ap.translate_fill[c] = int(v)
-            elif isinstance(op, Cutout):
-                ap.steps[i], cut = L.AUG_CUTOUT, op
-                ap.cutout_size = int(op.crop_size)
-                fill = np.broadcast_to(np.asarray(op.fill).astype(np.uint8).reshape(-1), (3,))
-                for c in range(3):
-                    ap.cutout_fill[c] = int(fill[c])
-            else:
-                raise TypeError(f'{type(op).__name__} cannot be fused into SimpleRGBImageDecoder')
-        norm = self._fused_normalize
-
-        def draw_params(ss, H, W):
-            key = (int(ss.loader_seed), int(ss.epoch), H, W)
-            cached = getattr(self, '_dp_cache', None)
-            if cached is not None and cached[0] == key:
-                return cached[1]
-            p = L.DrawParams()
-            p.out_h, p.out_w = H, W
-            p.cutout_size = int(cut.crop_size) if cut is not None else 0
-            p.flip_prob = float(flip.flip_prob) if flip is not None else 0.0
-            p.loader_seed = int(ss.loader_seed) & 0xFFFFFFFFFFFFFFFF
-            p.epoch = int(ss.epoch)
-            self._dp_cache = (key, p)
-            return p
+        ap, tr = self._aug_params()
+        ep = self._epilogue
+        flip, cut, norm = ep.flip, ep.cutout, ep.normalize
 
         def decode(batch_indices, storage, metadata, ss):
             out, smp, status, tyx, cyx, flips = storage
@@ -255,7 +248,8 @@ instead."""
             H, W = int(out.shape[1]), int(out.shape[2])
             samples = ss.batch_samples(f_ix, smp)
             if flip is not None or cut is not None:
-                L.draw_batch(ss.batch_ids, None, draw_params(ss, H, W), None, cyx if cut is not None else None,
+                L.draw_batch(ss.batch_ids, None, ep.draw_params(ss.loader_seed, ss.epoch, H, W), None,
+                             cyx if cut is not None else None,
                              flips if flip is not None else None, None, stream)
             if tr is not None:
                 L.translate_draw_batch(ss.batch_ids, ss.loader_seed, ss.epoch, ap.padding, tyx, None, stream)
@@ -275,21 +269,9 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
     def __init__(self, output_size):
         super().__init__()
         self.output_size = output_size
-        self._fused_cutout = None
-        self._fused_flip = None
-        self._cutout_before_flip = False
-        self._fused_normalize = None
 
-    # graph lowering hooks -------------------------------------------------
-    def fuse(self, cutout=None, flip=None, cutout_before_flip=False, normalize=None):
-        self._fused_cutout = cutout
-        self._fused_flip = flip
-        self._cutout_before_flip = cutout_before_flip
-        self._fused_normalize = normalize
-
-    @property
-    def output_dtype(self):
-        return ch.float16 if self._fused_normalize is not None else ch.uint8
+    # graph lowering hook: (cutout, flip, cutout_before_flip, normalize)
+    fuse = FusesEpilogue.fuse
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, AllocationQuery]:
         widths = self.metadata['width']
@@ -315,31 +297,17 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
              AllocationQuery((1,), ch.int32, dev)),  # decode status
         )
 
-    def _draw_params(self, ss, out_h, out_w):
-        key = (int(ss.loader_seed), int(ss.epoch), out_h, out_w)
-        cached = getattr(self, '_dp_cache', None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        p = self._make_draw_params(ss, out_h, out_w)
-        self._dp_cache = (key, p)
-        return p
-
-    def _make_draw_params(self, ss, out_h, out_w):
-        from .. import libffcv as L
-        p = L.DrawParams()
+    def _crop_fields(self, p):
+        """This decoder's crop draw, on top of the epilogue's DrawParams."""
         p.crop_kind = self.crop_kind
-        p.out_h, p.out_w = out_h, out_w
         if self.crop_kind == 0:
             p.scale[0], p.scale[1] = float(self.scale[0]), float(self.scale[1])
             p.ratio[0], p.ratio[1] = float(self.ratio[0]), float(self.ratio[1])
         else:
             p.center_ratio = float(self.ratio)
-        p.cutout_size = int(self._fused_cutout.crop_size) if self._fused_cutout is not None else 0
-        if self._fused_flip is not None:
-            p.flip_prob = float(self._fused_flip.flip_prob)
-        p.loader_seed = int(ss.loader_seed) & 0xFFFFFFFFFFFFFFFF
-        p.epoch = int(ss.epoch)
-        return p
+
+    def _draw_params(self, seed, epoch, out_h, out_w):
+        return self._epilogue.draw_params(seed, epoch, out_h, out_w, self._crop_fields)
 
     def _generate_code_host(self) -> Callable:
         """The reference's per-sample loop (rgb_image.py:185-210) on host
@@ -348,6 +316,7 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
         from ..pipeline import runtime
         mem_read = self.memory_read
         jpg = IMAGE_MODES['jpg']
+        no_epilogue = Epilogue()  # host Cutout / flip run as their own operations
 
         def decode(batch_indices, my_storage, metadata, storage_state):
             destination, temp_storage = my_storage
@@ -357,7 +326,7 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
             ctx = runtime.current()
             seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx is not None else (0, 0)
             out_h, out_w = int(destination.shape[1]), int(destination.shape[2])
-            dp = self._make_draw_params_seed(seed, epoch, out_h, out_w)
+            dp = no_epilogue.draw_params(seed, epoch, out_h, out_w, self._crop_fields)
             crops = np.empty((B, 4), np.int32)
             L.draw_batch_host(ids, fields['height'], fields['width'], dp, crops)
             # imdecode -> crop -> resize per sample, the reference's prange loop
@@ -372,32 +341,16 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
         decode.is_parallel = True
         return decode
 
-    def _make_draw_params_seed(self, seed, epoch, out_h, out_w):
-        class _S:
-            pass
-        ss = _S()
-        ss.loader_seed, ss.epoch = seed, epoch
-        p = self._make_draw_params(ss, out_h, out_w)
-        p.cutout_size = 0  # host Cutout / flip run as their own operations
-        p.flip_prob = 0.0
-        return p
-
     def generate_code(self) -> Callable:
         from .. import libffcv as L
         if not getattr(self, '_on_device', True):
             return self._generate_code_host()
         f_ix = self._field_index
-        rp = L.RRCParams()
-        cut = self._fused_cutout
-        if cut is not None:
-            rp.cutout_size = int(cut.crop_size)
-            fill = np.asarray(cut.fill).astype(np.uint8).reshape(-1)
-            fill = np.broadcast_to(fill, (3,)) if fill.size == 1 else fill
-            for i in range(3):
-                rp.cutout_fill[i] = int(fill[i])
-            rp.cutout_fill[3] = int(self._cutout_before_flip)
-        norm = self._fused_normalize
-        use_flip = self._fused_flip is not None
+        ep = self._epilogue
+        rp = ep.fill_rrc_params(L.RRCParams())
+        cut, norm = ep.cutout, ep.normalize
+        use_flip = ep.flip is not None
+        crop_fields = self._crop_fields
 
         def decode(batch_indices, storage, metadata, ss):
             out, smp, crops, cyx, flips, status = storage
@@ -407,7 +360,7 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
             # resize_crop(..., destination[dst_ix]) (rgb_image.py:207-208):
             # a new output_size between epochs gets new buffers and is used
             rp.out_h, rp.out_w = int(out.shape[1]), int(out.shape[2])
-            dp = self._draw_params(ss, rp.out_h, rp.out_w)
+            dp = ep.draw_params(ss.loader_seed, ss.epoch, rp.out_h, rp.out_w, crop_fields)
             if norm is not None:
                 rp.lut = norm.device_lut(out.device).data_ptr()
             rp.out_stride = out[0].numel() * out.element_size()

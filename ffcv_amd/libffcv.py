@@ -570,6 +570,11 @@ def _seed64(loader_seed):
     return int(loader_seed) & 0xFFFFFFFFFFFFFFFF
 
 
+def fill_u8(fill):
+    """A fill colour (a number, or one or three of them) as a fresh (3,) uint8 array."""
+    return np.broadcast_to(np.asarray(fill).astype(np.uint8).reshape(-1), (3,)).copy()
+
+
 def _u8_batch_dims(images, who):
     """(B, H, W) of a contiguous uint8 (B, H, W, 3) batch: a numpy array for a
     ``*_host`` entry, else a tensor."""
@@ -1022,13 +1027,6 @@ def _ranges12(ranges):
     return r
 
 
-def _fill3(fill):
-    f = np.ascontiguousarray(fill, dtype=np.uint8).reshape(-1)
-    if f.shape != (3,):
-        raise TypeError('fill must be three uint8 values')
-    return f
-
-
 def affine_draw_batch(ids, loader_seed, epoch, p, ranges, height, width, apply, coef, status=None, stream=None):
     """RandomAffine's seven draws of the batch and their Q16 coefficients on
     the device (op id 14): apply uint8[B], coef int64 (B, 6)."""
@@ -1082,7 +1080,7 @@ def affine_batch(src, dst, mode, fill, apply, coef, dst_stride=0, stream=None):
     if src.dim() != 4 or int(src.shape[3]) != 3 or src.element_size() != 1 or not src.is_contiguous():
         raise TypeError('affine_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
     B, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
-    f = _fill3(fill)
+    f = fill_u8(fill)
     _check(lib().ffcv_affine_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef),
                                    int(dst_stride)), 'ffcv_affine_batch')
     return dst
@@ -1095,7 +1093,7 @@ def affine_batch_host(src: np.ndarray, dst: np.ndarray, mode, fill, apply, coef,
             dst.flags.c_contiguous and dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
         raise TypeError('affine_batch_host: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are required')
     B, H, W = (int(x) for x in src.shape[:3])
-    f = _fill3(fill)
+    f = fill_u8(fill)
     apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
     coef = np.ascontiguousarray(coef, np.int64)
     if apply.size != B or coef.shape != (B, 6):

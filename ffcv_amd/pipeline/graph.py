@@ -173,21 +173,17 @@ class Graph:
         for chain in self._chains.values():
             self._lower_rrc_transform(chain)
 
-    def _scan_epilogue(self, ops):
-        """The operations a crop-and-resize launch can apply itself, scanned
-        through ToTensor, same-device ToDevice and ToTorchImage: Cutout and
-        RandomHorizontalFlip (each once, their order recorded, before any
-        layout change) and NormalizeImage(float16) with a (256, 3) table.
-        They are marked absorbed (they run as identities).  Returns (cutout,
-        flip, cutout_before_flip, normalize)."""
-        from ..transforms import (Cutout, RandomHorizontalFlip, NormalizeImage, ToTensor, ToDevice,
-                                  ToTorchImage)
-        cutout = flip = norm = None
-        cut_before_flip = False
+    def _absorbable(self, ops):
+        """The operations behind a launch that it may apply itself, each with
+        whether the layout has changed in front of it: ToTensor and a
+        same-device ToDevice are passed, ToTorchImage is passed and noted, and
+        an operation that another pipeline shares ends the walk.  The caller
+        stops the walk at the first operation it does not take."""
+        from ..transforms import ToTensor, ToDevice, ToTorchImage
         layout_changed = False
         for op in ops:
             if len(self.operation_to_node[op]) != 1:
-                break
+                return
             if isinstance(op, ToTensor):
                 continue
             if isinstance(op, ToTorchImage):
@@ -197,25 +193,39 @@ class Graph:
                 t = ch.device(op.device)
                 if t.type == 'cuda' and (t.index is None or t.index == (self.device.index or 0)):
                     continue
-                break
+                return
+            yield op, layout_changed
+
+    @staticmethod
+    def _is_fp16_table(op):
+        """NormalizeImage(float16) with a (256, 3) table: the one a launch's store applies."""
+        from ..transforms import NormalizeImage
+        return isinstance(op, NormalizeImage) and np.dtype(op.original_dtype) == np.float16 and \
+            np.asarray(op.lookup_table).shape == (256, 3)
+
+    def _scan_epilogue(self, ops):
+        """The operations a crop-and-resize launch can apply itself: Cutout
+        and RandomHorizontalFlip (each once, their order recorded, before any
+        layout change) and then NormalizeImage(float16), which ends the scan.
+        They are marked absorbed (they run as identities).  Returns (cutout,
+        flip, cutout_before_flip, normalize)."""
+        from ..transforms import Cutout, RandomHorizontalFlip
+        cutout = flip = norm = None
+        cut_before_flip = False
+        for op, layout_changed in self._absorbable(ops):
             if getattr(op, '_absorbed', False):
                 break
-            if isinstance(op, Cutout) and cutout is None and norm is None and not layout_changed:
-                cutout = op
-                cut_before_flip = flip is None
-                op._absorbed = True
-                continue
-            if isinstance(op, RandomHorizontalFlip) and flip is None and norm is None \
-                    and not layout_changed:
+            if isinstance(op, Cutout) and cutout is None and not layout_changed:
+                cutout, cut_before_flip = op, flip is None
+            elif isinstance(op, RandomHorizontalFlip) and flip is None and not layout_changed:
                 flip = op
-                op._absorbed = True
-                continue
-            if isinstance(op, NormalizeImage) and norm is None and \
-                    np.dtype(op.original_dtype) == np.float16 and \
-                    np.asarray(op.lookup_table).shape == (256, 3):
+            elif self._is_fp16_table(op):
                 norm = op
-                op._absorbed = True
-            break
+            else:
+                break
+            op._absorbed = True
+            if norm is not None:
+                break
         return cutout, flip, cut_before_flip, norm
 
     def _lower_rrc_transform(self, chain):
@@ -245,31 +255,15 @@ class Graph:
         (ffcv_simple_aug_batch).  Only chains that contain a RandomTranslate
         are lowered; every other Simple-decoder chain, and any field with a
         JPEG-mode sample, keeps its staged launches."""
-        from ..transforms import (Cutout, RandomHorizontalFlip, RandomTranslate, NormalizeImage, ToTensor,
-                                  ToDevice, ToTorchImage)
+        from ..transforms import Cutout, RandomHorizontalFlip, RandomTranslate
         dec = chain[0]
         steps, norm = [], None
-        layout_changed = False
-        for op in chain[1:]:
-            if len(self.operation_to_node[op]) != 1:
-                break
-            if isinstance(op, ToTensor):
-                continue
-            if isinstance(op, ToTorchImage):
-                layout_changed = True
-                continue
-            if isinstance(op, ToDevice):
-                t = ch.device(op.device)
-                if t.type == 'cuda' and (t.index is None or t.index == (self.device.index or 0)):
-                    continue
-                break
-            if isinstance(op, (Cutout, RandomHorizontalFlip, RandomTranslate)) and norm is None \
-                    and not layout_changed and not any(type(s) is type(op) for s in steps):
+        for op, layout_changed in self._absorbable(chain[1:]):
+            if isinstance(op, (Cutout, RandomHorizontalFlip, RandomTranslate)) and not layout_changed \
+                    and not any(type(s) is type(op) for s in steps):
                 steps.append(op)
                 continue
-            if isinstance(op, NormalizeImage) and norm is None and \
-                    np.dtype(op.original_dtype) == np.float16 and \
-                    np.asarray(op.lookup_table).shape == (256, 3):
+            if self._is_fp16_table(op):
                 norm = op
             break
         fix = self.operation_to_node[dec][0].f_ix

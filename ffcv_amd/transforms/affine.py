@@ -23,6 +23,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch as ch
 
+from ..libffcv import fill_u8
 from ..pipeline.allocation_query import AllocationQuery
 from ..pipeline.state import State
 from ..pipeline import runtime
@@ -119,7 +120,7 @@ class RandomAffine(_U8ImageOp):
         self.p = self.check_p(name, p)
 
     def fill_u8(self):
-        return np.broadcast_to(np.asarray(self.fill).astype(np.uint8).reshape(-1), (3,)).copy()
+        return fill_u8(self.fill)
 
     def ranges(self, height, width):
         """The six (low, high) pairs of the draws for height x width images."""

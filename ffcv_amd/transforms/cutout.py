@@ -15,15 +15,16 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch as ch
 
+from ..libffcv import fill_u8
 from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
+from ..pipeline.epilogue import Epilogue
 from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
-from .u8_image import check_u8_images
+from .u8_image import _U8ImageOp
 
 
-class Cutout(Operation):
+class Cutout(_U8ImageOp):
     """Cutout data augmentation (https://arxiv.org/abs/1708.04552).
 
     Parameters
@@ -33,22 +34,18 @@ class Cutout(Operation):
     fill : Tuple[int, int, int], optional
         An RGB color ((0, 0, 0) by default) to fill the cutout square with.
     """
-    device_aware = True
-    per_sample = True
 
     def __init__(self, crop_size: int, fill: Tuple[int, int, int] = (0, 0, 0)):
         super().__init__()
         self.crop_size = crop_size
         self.fill = np.array(fill)
-        self._absorbed = False
 
     def generate_code(self) -> Callable:
         if self._absorbed:
-            def fused(images, *_):
-                return images
-            return fused
+            return self.identity()
         crop_size = int(self.crop_size)
-        fill = np.broadcast_to(np.asarray(self.fill).astype(np.uint8).reshape(-1), (3,)).copy()
+        fill = fill_u8(self.fill)
+        draws = Epilogue(cutout=self)
 
         def cutout_square(images, dst, indices):
             ctx = runtime.current()
@@ -56,10 +53,7 @@ class Cutout(Operation):
                 from .. import libffcv as L
                 B = images.shape[0]
                 yx = ch.empty((B, 2), dtype=ch.int32, device=images.device)
-                p = L.DrawParams()
-                p.out_h, p.out_w = int(images.shape[1]), int(images.shape[2])
-                p.cutout_size = crop_size
-                p.loader_seed, p.epoch = int(ctx.loader_seed), int(ctx.epoch)
+                p = draws.draw_params(ctx.loader_seed, ctx.epoch, int(images.shape[1]), int(images.shape[2]))
                 L.draw_batch(ctx.batch_ids, None, p, None, yx, None, None, ctx.stream)
                 L.cutout_batch(images, yx, crop_size, fill, ctx.stream)
                 return images
@@ -76,6 +70,6 @@ class Cutout(Operation):
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         if previous_state.device.type == 'cuda' and not self._absorbed:   # the device kernel reads (B, H, W, 3) uint8
-            check_u8_images('Cutout', previous_state)
+            self.check_u8_images(previous_state)
         return replace(previous_state, jit_mode=previous_state.device.type == 'cpu'
                        and not isinstance(previous_state.dtype, ch.dtype)), None

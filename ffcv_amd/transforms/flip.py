@@ -7,21 +7,20 @@ decoder; otherwise a device kernel or host numpy.  On the device it takes
 uint8 (H, W, 3) images only: behind ToTorchImage, NormalizeImage or Convert it
 refuses the pipeline.
 """
-from dataclasses import replace
 from typing import Callable, Optional, Tuple
 
 import numpy as np
 import torch as ch
 
 from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
+from ..pipeline.epilogue import Epilogue
 from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
-from .u8_image import check_u8_images
+from .u8_image import _U8ImageOp
 
 
-class RandomHorizontalFlip(Operation):
+class RandomHorizontalFlip(_U8ImageOp):
     """Flip the image horizontally with probability flip_prob.
 
     Parameters
@@ -29,20 +28,16 @@ class RandomHorizontalFlip(Operation):
     flip_prob : float
         The probability with which to flip each image in the batch horizontally.
     """
-    device_aware = True
-    per_sample = True
 
     def __init__(self, flip_prob: float = 0.5):
         super().__init__()
         self.flip_prob = flip_prob
-        self._absorbed = False
 
     def generate_code(self) -> Callable:
         if self._absorbed:
-            def fused(images, dst, *_):
-                return images
-            return fused
+            return self.identity()
         flip_prob = float(self.flip_prob)
+        draws = Epilogue(flip=self)
 
         def flip(images, dst, indices):
             ctx = runtime.current()
@@ -50,9 +45,7 @@ class RandomHorizontalFlip(Operation):
                 from .. import libffcv as L
                 B = images.shape[0]
                 flips = ch.empty(B, dtype=ch.uint8, device=images.device)
-                p = L.DrawParams()
-                p.flip_prob = flip_prob
-                p.loader_seed, p.epoch = int(ctx.loader_seed), int(ctx.epoch)
+                p = draws.draw_params(ctx.loader_seed, ctx.epoch, 0, 0)
                 L.draw_batch(ctx.batch_ids, None, p, None, None, flips, None, ctx.stream)
                 out = dst[:B]
                 L.flip_batch(images, out, flips, ctx.stream)
@@ -69,9 +62,6 @@ class RandomHorizontalFlip(Operation):
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         if self._absorbed:
             return previous_state, None
-        on_dev = previous_state.device.type == 'cuda'
-        if on_dev:   # the device kernel reads (B, H, W, 3) uint8
-            check_u8_images('RandomHorizontalFlip', previous_state)
-        return (replace(previous_state, jit_mode=not on_dev and not isinstance(previous_state.dtype, ch.dtype)),
-                AllocationQuery(previous_state.shape, previous_state.dtype,
-                                previous_state.device if on_dev else None))
+        if previous_state.device.type == 'cuda':   # the device kernel reads (B, H, W, 3) uint8
+            self.check_u8_images(previous_state)
+        return self.declare_out_of_place(previous_state)

@@ -19,6 +19,7 @@ from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
 from .lut import make_lut
+from .u8_image import _U8ImageOp
 
 
 def ch_dtype_from_numpy(dtype):
@@ -61,9 +62,7 @@ class NormalizeImage(Operation):
 
     def generate_code(self) -> Callable:
         if self._absorbed:
-            def fused(images, *_):
-                return images
-            return fused
+            return _U8ImageOp.identity()
         if self.mode == 'cpu':
             return self.generate_code_cpu()
         return self.generate_code_gpu()

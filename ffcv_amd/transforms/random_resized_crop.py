@@ -26,12 +26,14 @@ import numpy as np
 import torch as ch
 
 from ..pipeline.allocation_query import AllocationQuery
+from ..pipeline.epilogue import FusesEpilogue
 from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
+from .u8_image import check_u8_images
 
 
-class RandomResizedCrop(Operation):
+class RandomResizedCrop(FusesEpilogue, Operation):
     """Crop a random portion of image with random aspect ratio and resize it to
     a given size.
 
@@ -54,22 +56,13 @@ class RandomResizedCrop(Operation):
         self.scale = scale
         self.ratio = ratio
         self.size = int(size)
-        self._fused_cutout = None
-        self._fused_flip = None
-        self._cutout_before_flip = False
-        self._fused_normalize = None
-
-    # graph lowering hook: the Cutout / RandomHorizontalFlip / fp16
-    # NormalizeImage behind this transform that its launch applies
-    def fuse(self, cutout=None, flip=None, cutout_before_flip=False, normalize=None):
-        self._fused_cutout = cutout
-        self._fused_flip = flip
-        self._cutout_before_flip = cutout_before_flip
-        self._fused_normalize = normalize
+        # graph lowering hook (fuse): the Cutout / RandomHorizontalFlip / fp16
+        # NormalizeImage behind this transform that its launch applies
+        self.fuse()
 
     @property
     def fused(self):
-        return any(x is not None for x in (self._fused_cutout, self._fused_flip, self._fused_normalize))
+        return bool(self._epilogue)
 
     def _ranges(self):
         scale = tuple(float(x) for x in np.asarray(self.scale, np.float64).reshape(-1))
@@ -83,19 +76,10 @@ class RandomResizedCrop(Operation):
         from .. import libffcv as L
         scale, ratio = self._ranges()
         size = self.size
-        cut, flip, norm = self._fused_cutout, self._fused_flip, self._fused_normalize
-        rp = L.RRCParams()
+        ep = self._epilogue
+        cut, flip, norm = ep.cutout, ep.flip, ep.normalize
+        rp = ep.fill_rrc_params(L.RRCParams())
         rp.out_h = rp.out_w = size
-        if cut is not None:
-            rp.cutout_size = int(cut.crop_size)
-            fill = np.broadcast_to(np.asarray(cut.fill).astype(np.uint8).reshape(-1), (3,))
-            for i in range(3):
-                rp.cutout_fill[i] = int(fill[i])
-            rp.cutout_fill[3] = int(self._cutout_before_flip)
-        dp = L.DrawParams()
-        dp.out_h = dp.out_w = size
-        dp.cutout_size = int(cut.crop_size) if cut is not None else 0
-        dp.flip_prob = float(flip.flip_prob) if flip is not None else 0.0
         key = ('rrc_transform', id(self))
 
         def random_resized_crop(images, storage, indices):
@@ -109,7 +93,7 @@ class RandomResizedCrop(Operation):
                 L.crop_draw_batch(ctx.batch_ids, H, W, scale, ratio, ctx.loader_seed, ctx.epoch, crops, None, stream)
                 cyx = flips = None
                 if cut is not None or flip is not None:
-                    dp.loader_seed, dp.epoch = int(ctx.loader_seed) & 0xFFFFFFFFFFFFFFFF, int(ctx.epoch)
+                    dp = ep.draw_params(ctx.loader_seed, ctx.epoch, size, size)
                     if cut is not None:
                         cyx = ctx.device_buffer(key + ('cut',), 2 * ctx.batch_size, ch.int32)
                     if flip is not None:
@@ -146,16 +130,12 @@ class RandomResizedCrop(Operation):
         return random_resized_crop
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
-        dt, shape = previous_state.dtype, previous_state.shape
-        is_u8 = dt == ch.uint8 if isinstance(dt, ch.dtype) else np.dtype(dt) == np.uint8
-        if not is_u8 or shape is None or len(shape) != 3 or shape[2] != 3:
-            raise TypeError(f'RandomResizedCrop works on uint8 (H, W, 3) images, got {dt} {tuple(shape or ())}: '
-                            'place it before ToTorchImage / NormalizeImage / Convert')
+        dt, _ = check_u8_images('RandomResizedCrop', previous_state)
         self._ranges()
         out_shape = (self.size, self.size, 3)
         on_dev = previous_state.device.type == 'cuda'
         if on_dev:
-            out_dt = ch.float16 if self._fused_normalize is not None else dt
+            out_dt = self._epilogue.output_dtype(dt)
             return (replace(previous_state, jit_mode=False, shape=out_shape, dtype=out_dt),
                     (AllocationQuery(out_shape, out_dt, previous_state.device),
                      AllocationQuery((4,), ch.int32, previous_state.device)))   # crop window

@@ -15,18 +15,17 @@ it takes uint8 (H, W, 3) images only: behind ToTorchImage, NormalizeImage or
 Convert it refuses the pipeline.
 """
 import numbers
-from dataclasses import replace
 from typing import Callable, Optional, Tuple
 
 import numpy as np
 import torch as ch
 
+from ..libffcv import fill_u8
 from ..pipeline.allocation_query import AllocationQuery
-from ..pipeline.operation import Operation
 from ..pipeline.state import State
 from ..pipeline import runtime
 from .rng import contract_seed
-from .u8_image import check_u8_images
+from .u8_image import _U8ImageOp
 
 
 def translate_window(image, dst, y, x, padding, fill):
@@ -43,7 +42,7 @@ def translate_window(image, dst, y, x, padding, fill):
     return dst
 
 
-class RandomTranslate(Operation):
+class RandomTranslate(_U8ImageOp):
     """Translate each image randomly in vertical and horizontal directions
     up to specified number of pixels.
 
@@ -54,8 +53,6 @@ class RandomTranslate(Operation):
     fill : tuple
         An RGB color ((0, 0, 0) by default) to fill the area outside the shifted image.
     """
-    device_aware = True
-    per_sample = True
 
     def __init__(self, padding: int, fill: Tuple[int, int, int] = (0, 0, 0)):
         super().__init__()
@@ -63,16 +60,13 @@ class RandomTranslate(Operation):
             raise ValueError(f'RandomTranslate: padding must be an int >= 0, got {padding!r}')
         self.padding = int(padding)
         self.fill = np.array(fill)
-        self._absorbed = False
 
     def fill_u8(self):
-        return np.broadcast_to(np.asarray(self.fill).astype(np.uint8).reshape(-1), (3,)).copy()
+        return fill_u8(self.fill)
 
     def generate_code(self) -> Callable:
         if self._absorbed:
-            def fused(images, dst, *_):
-                return images
-            return fused
+            return self.identity()
         pad = self.padding
         fill = self.fill_u8()
 
@@ -100,9 +94,6 @@ class RandomTranslate(Operation):
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         if self._absorbed:
             return previous_state, None
-        on_dev = previous_state.device.type == 'cuda'
-        if on_dev:   # the device kernel reads (B, H, W, 3) uint8
-            check_u8_images('RandomTranslate', previous_state)
-        return (replace(previous_state, jit_mode=not on_dev and not isinstance(previous_state.dtype, ch.dtype)),
-                AllocationQuery(previous_state.shape, previous_state.dtype,
-                                previous_state.device if on_dev else None))
+        if previous_state.device.type == 'cuda':   # the device kernel reads (B, H, W, 3) uint8
+            self.check_u8_images(previous_state)
+        return self.declare_out_of_place(previous_state)

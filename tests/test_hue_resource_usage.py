@@ -14,14 +14,9 @@ all 32 waves of a CU, share its 160 KiB).  Each kernel is pinned to its count,
 so that a change that costs registers or occupancy fails here; one that saves
 some lowers the bound.
 """
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'ffcv_amd', 'csrc')
+from tests.resource_usage import find, kernel_usage
 
 # kernel name fragment -> (VGPRs, waves/SIMD)
 BUDGET = {
@@ -35,44 +30,19 @@ LDS_LIMIT = 160 * 1024 // 8   # eight workgroups per CU
 @pytest.fixture(scope='module')
 def usage():
     from ffcv_amd import _build
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    if not os.path.exists(hipcc):
-        pytest.skip('hipcc not available')
     assert 'ffcv_hue.hip' in _build.SOURCES and 'hue_common.h' in _build.HEADERS
-    flags = [f for f in _build.FLAGS if f != '-shared']
-    cmd = [hipcc] + flags + ['--cuda-device-only', '-c', '-Rpass-analysis=kernel-resource-usage', '-o', os.devnull,
-                             'ffcv_hue.hip']
-    err = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stderr
-    out, cur = {}, None
-    for line in err.splitlines():
-        m = re.search(r'remark:\s+(.*?) \[-Rpass-analysis', line)
-        if not m:
-            continue
-        key, _, val = m.group(1).strip().partition(':')
-        if key == 'Function Name':
-            cur = out.setdefault(val.strip(), {})
-        elif cur is not None and val.strip().lstrip('-').isdigit():
-            cur[key.strip()] = int(val)
-    return out
-
-
-def _find(usage, frag):
-    """The kernel whose mangled name carries exactly this name (hue_kernel is
-    not a fragment of hue_draw_kernel, but stay exact: <length><name>)."""
-    hits = [v for k, v in usage.items() if f'{len(frag)}{frag}' in k]
-    assert len(hits) == 1, (frag, sorted(usage))
-    return hits[0]
+    return kernel_usage('ffcv_hue.hip')
 
 
 def test_every_kernel_is_reported(usage):
     assert len(usage) == len(BUDGET), sorted(usage)
     for frag in BUDGET:
-        _find(usage, frag)
+        find(usage, frag)
 
 
 @pytest.mark.parametrize('frag', sorted(BUDGET))
 def test_no_scratch_no_spills_and_pinned_registers(usage, frag):
-    u = _find(usage, frag)
+    u = find(usage, frag)
     print(frag, u)
     vgprs, occupancy = BUDGET[frag]
     assert u['ScratchSize [bytes/lane]'] == 0

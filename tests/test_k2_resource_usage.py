@@ -11,14 +11,9 @@ the rest to the general per-pixel path, which keeps the image record's head
 (DESIGN.md s3 lists them).  Each instantiation is pinned to its own count, so
 that any new spill fails here; a change that removes some lowers the bound.
 """
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'ffcv_amd', 'csrc')
+from tests.resource_usage import kernel_usage
 
 K1 = '_Z19jpeg_entropy_kernelILi0EEv8JpegArgs'
 K1B = '_Z16jpeg_idct_kernel8JpegArgs'
@@ -28,25 +23,7 @@ K2_U8 = '_Z24jpeg_color_resize_kernelILi0ELb0EEv8JpegArgs'
 
 @pytest.fixture(scope='module')
 def usage():
-    from ffcv_amd import _build
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    if not os.path.exists(hipcc):
-        pytest.skip('hipcc not available')
-    flags = [f for f in _build.FLAGS if f != '-shared']
-    cmd = [hipcc] + flags + ['--cuda-device-only', '-c', '-Rpass-analysis=kernel-resource-usage', '-o', os.devnull,
-                             'ffcv_jpeg.hip']
-    err = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stderr
-    out, cur = {}, None
-    for line in err.splitlines():
-        m = re.search(r'remark:\s+(.*?) \[-Rpass-analysis', line)
-        if not m:
-            continue
-        key, _, val = m.group(1).strip().partition(':')
-        if key == 'Function Name':
-            cur = out.setdefault(val.strip(), {})
-        elif cur is not None and val.strip().lstrip('-').isdigit():
-            cur[key.strip()] = int(val)
-    return out
+    return kernel_usage('ffcv_jpeg.hip')
 
 
 @pytest.mark.parametrize('kernel,spills', [(K2_FP16, 55), (K2_U8, 55)])

@@ -15,14 +15,9 @@ LDS: the staged source, the taps and the LUT).  Each kernel is pinned to its
 count, so that a change that costs registers or occupancy fails here; one
 that saves some lowers the bound.
 """
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'ffcv_amd', 'csrc')
+from tests.resource_usage import kernel_usage
 
 # kernel name fragment -> (VGPRs, waves/SIMD)
 BUDGET = {
@@ -36,25 +31,8 @@ BUDGET = {
 @pytest.fixture(scope='module')
 def usage():
     from ffcv_amd import _build
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    if not os.path.exists(hipcc):
-        pytest.skip('hipcc not available')
     assert 'ffcv_rrc_images.hip' in _build.SOURCES
-    flags = [f for f in _build.FLAGS if f != '-shared']
-    cmd = [hipcc] + flags + ['--cuda-device-only', '-c', '-Rpass-analysis=kernel-resource-usage', '-o', os.devnull,
-                             'ffcv_rrc_images.hip']
-    err = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stderr
-    out, cur = {}, None
-    for line in err.splitlines():
-        m = re.search(r'remark:\s+(.*?) \[-Rpass-analysis', line)
-        if not m:
-            continue
-        key, _, val = m.group(1).strip().partition(':')
-        if key == 'Function Name':
-            cur = out.setdefault(val.strip(), {})
-        elif cur is not None and val.strip().lstrip('-').isdigit():
-            cur[key.strip()] = int(val)
-    return out
+    return kernel_usage('ffcv_rrc_images.hip')
 
 
 def test_every_kernel_is_reported(usage):
