@@ -2,8 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <thread>
+#include <vector>
 
 #include "../../include/ffcv_hip.h"
 
@@ -74,6 +78,22 @@ int host_draw(const char *who, int batch, F draw_one) {
     return FFCV_EINVAL;
   }
   return FFCV_OK;
+}
+
+// The threads of a host twin over n items: body(next, tid, T) runs on
+// T = min(max(nthreads, 1), n) threads (at least one), the caller among them
+// as tid 0, and all are joined before this returns.  next: a counter from 0
+// that the bodies share to claim items one at a time (fetch_add); tid and T
+// serve a static split instead.  A thread's scratch lives at the top of body.
+template <class F>
+void host_threads(int nthreads, int64_t n, F body) {
+  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(nthreads, n));
+  std::atomic<uint64_t> next{0};
+  std::vector<std::thread> th;
+  th.reserve(T - 1);
+  for (int t = 1; t < T; t++) th.emplace_back([&body, &next, t, T] { body(next, t, T); });
+  body(next, 0, T);
+  for (auto &x : th) x.join();
 }
 
 }  // namespace ffcv

@@ -29,12 +29,8 @@
 //     staged once as one byte range.
 //   tiles: AFFINE_TILE_ROWS x AFFINE_TILE_COLS outputs; the staged footprint
 //     takes at most AFFINE_TILE_LDS bytes.
-#include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstring>
-#include <thread>
-#include <vector>
 
 #include "affine_common.h"
 #include "api_internal.h"
@@ -430,23 +426,16 @@ int ffcv_affine_batch_host(const uint8_t *src, uint8_t *dst, int batch, int heig
   if (batch == 0) return FFCV_OK;
   const uint64_t img = (uint64_t)height * width * 3;
   const uint32_t f = pack_fill(fill);
-  std::atomic<int> next{0};
-  auto work = [&]() {
-    for (int k = next.fetch_add(1); k < batch; k = next.fetch_add(1)) {
-      const uint8_t *in = src + (uint64_t)k * img;
-      uint8_t *out = dst + (uint64_t)k * stride;
+  ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
+    for (uint64_t k = next.fetch_add(1); k < (uint64_t)batch; k = next.fetch_add(1)) {
+      const uint8_t *in = src + k * img;
+      uint8_t *out = dst + k * stride;
       if (apply[k])
-        affine_image_host(in, out, height, width, mode, f, coef + (uint64_t)k * 6);
+        affine_image_host(in, out, height, width, mode, f, coef + k * 6);
       else
         std::memcpy(out, in, img);
     }
-  };
-  const int T = std::max(1, std::min(nthreads, batch));
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work);
-  work();
-  for (auto &x : th) x.join();
+  });
   return FFCV_OK;
 }
 

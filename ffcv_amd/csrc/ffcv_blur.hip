@@ -29,12 +29,8 @@
 //     plane exceed BLUR_TILE_LDS at the image's width is split into column
 //     strips of the widest width that fits (blur_strip_cols).  A tile takes
 //     at most 40 KiB: four workgroups per CU again.
-#include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstring>
-#include <thread>
-#include <vector>
 
 #include "api_internal.h"
 #include "blur_common.h"
@@ -410,24 +406,17 @@ int ffcv_gaussian_blur_batch_host(const uint8_t *src, uint8_t *dst, int batch, i
     return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
   const uint64_t img = (uint64_t)height * width * 3;
-  std::atomic<int> next{0};
-  auto work = [&]() {
+  ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
     std::vector<float> plane;
-    for (int k = next.fetch_add(1); k < batch; k = next.fetch_add(1)) {
-      const uint8_t *in = src + (uint64_t)k * img;
-      uint8_t *out = dst + (uint64_t)k * stride;
+    for (uint64_t k = next.fetch_add(1); k < (uint64_t)batch; k = next.fetch_add(1)) {
+      const uint8_t *in = src + k * img;
+      uint8_t *out = dst + k * stride;
       if (apply[k])
-        blur_image_host(in, out, height, width, ksize, weights + (uint64_t)k * FFCV_BLUR_WROW, plane);
+        blur_image_host(in, out, height, width, ksize, weights + k * FFCV_BLUR_WROW, plane);
       else
         std::memcpy(out, in, img);
     }
-  };
-  const int T = std::max(1, std::min(nthreads, batch));
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work);
-  work();
-  for (auto &x : th) x.join();
+  });
   return FFCV_OK;
 }
 

@@ -6,10 +6,7 @@
 
 #include "api_internal.h"
 
-#include <algorithm>
 #include <cstring>
-#include <thread>
-#include <vector>
 
 namespace ffcv {
 static thread_local std::string g_last_error;
@@ -98,8 +95,7 @@ int ffcv_host_gather(const uint8_t *src, const uint64_t *src_off, const uint64_t
   }
   uint64_t total = 0;
   for (int i = 0; i < n; i++) total += sizes[i];
-  const int T = std::max(1, std::min(nthreads, n));
-  auto work = [&](int tid) {
+  ffcv::host_threads(nthreads, n, [&](std::atomic<uint64_t> &, int tid, int T) {
     // contiguous runs of samples with about total / T bytes each
     const uint64_t lo = total * tid / T, hi = total * (tid + 1) / T;
     uint64_t acc = 0;
@@ -110,16 +106,7 @@ int ffcv_host_gather(const uint8_t *src, const uint64_t *src_off, const uint64_t
       const uint64_t s = std::max(a, lo) - a, e = std::min(b, hi) - a;
       std::memcpy(dst + dst_off[i] + s, src + src_off[i] + s, e - s);
     }
-  };
-  if (T == 1) {
-    work(0);
-    return FFCV_OK;
-  }
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work, t);
-  work(0);
-  for (auto &x : th) x.join();
+  });
   return FFCV_OK;
 }
 

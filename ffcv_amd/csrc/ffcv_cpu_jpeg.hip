@@ -21,13 +21,10 @@
 // and 1/8 too (decode_scaled, jidctred.c): a request TurboJPEG would decode
 // at another factor returns -1.  ffcv itself passes the image's own size and
 // False, False, 1, 1.
-#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
-#include <vector>
 
 #include "api_internal.h"
 
@@ -1033,7 +1030,6 @@ int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, con
     ffcv::set_error("ffcv_cpu_decode_batch: invalid arguments");
     return FFCV_EINVAL;
   }
-  std::atomic<int> next{0};
   // the first failing sample's message: set_error is thread-local, so a
   // worker's message is copied here and re-raised on the calling thread
   std::mutex err_mu;
@@ -1047,9 +1043,9 @@ int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, con
       err_msg = msg;
     }
   };
-  auto work = [&]() {
+  ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
     std::vector<uint8_t> img;
-    for (int k = next.fetch_add(1); k < batch; k = next.fetch_add(1)) {
+    for (int k = (int)next.fetch_add(1); k < batch; k = (int)next.fetch_add(1)) {
       const uint32_t h = heights[k], w = widths[k], mode = modes[k];
       status[k] = 0;
       if (mode > 1) continue;
@@ -1082,13 +1078,7 @@ int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, con
                out_h, out_w);
       }
     }
-  };
-  const int T = std::max(1, std::min(nthreads, batch));
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work);
-  work();
-  for (auto &x : th) x.join();
+  });
   if (err_k < batch) ffcv::set_error("sample %d: %s", err_k, err_msg.c_str());
   return FFCV_OK;
 }

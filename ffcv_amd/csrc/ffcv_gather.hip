@@ -37,6 +37,7 @@
 //                                      in flight; rows beyond 65535 and chunks
 //                                      beyond the grid are looped over
 // GATHER_LARGE_BYTES was measured.
+// The decoders' two simple gathers (sample descriptors, raw sample bytes) live here too.
 #include "api_internal.h"
 
 #define GATHER_THREADS 256
@@ -46,6 +47,39 @@
 #define GATHER_CHUNK_VECS (GATHER_THREADS * GATHER_UNROLL)
 #define GATHER_MAX_GRID_X 4096
 #define GATHER_MAX_GRID_Y 65535
+
+// --------------------------------------------- simple (raw) gather -------
+__global__ void __launch_bounds__(256) gather_raw_kernel(const uint8_t *__restrict__ base,
+                                                         const ffcv_sample *__restrict__ samples,
+                                                         uint8_t *__restrict__ out, uint64_t stride) {
+  const int k = blockIdx.y;
+  const ffcv_sample s = samples[k];
+  if (s.mode != 1) return;
+  const uint8_t *src = base + s.offset;
+  uint8_t *dst = out + stride * k;
+  uint64_t n = s.size;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+    dst[i] = src[i];
+}
+
+__global__ void __launch_bounds__(256) gather_samples_kernel(const ffcv_sample *__restrict__ table, uint64_t n,
+                                                             const uint64_t *__restrict__ ids, int B,
+                                                             ffcv_sample *__restrict__ out) {
+  int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= B) return;
+  uint64_t i = ids[k];
+  ffcv_sample s;
+  if (i < n) {
+    s = table[i];
+  } else {  // out-of-range index: an empty jpg sample -> BAD_MARKER status
+    s.offset = 0;
+    s.size = 0;
+    s.height = s.width = 1;
+    s.mode = 0;
+    s.reserved = 0;
+  }
+  out[k] = s;
+}
 
 namespace {
 
@@ -186,6 +220,40 @@ enum { SHAPE_AUTO = 0, SHAPE_SUBWAVE = 1, SHAPE_WAVE = 2, SHAPE_GRID = 3 };
 }  // namespace
 
 extern "C" {
+
+int ffcv_gather_samples(void *stream, const ffcv_sample *table, uint64_t n_table, const uint64_t *ids,
+                        int batch, ffcv_sample *out) {
+  if (!table || !ids || !out || batch < 0) {
+    ffcv::set_error("ffcv_gather_samples: invalid arguments");
+    return FFCV_EINVAL;
+  }
+  if (batch == 0) return FFCV_OK;
+  hipLaunchKernelGGL(gather_samples_kernel, dim3((batch + 255) / 256), dim3(256), 0, ffcv::as_stream(stream),
+                     table, n_table, ids, batch, out);
+  FFCV_LAUNCH_CHECK("gather_samples_kernel");
+  return FFCV_OK;
+}
+
+// gather_raw_kernel takes the image from blockIdx.y, and a grid has at most
+// 65,535 rows: a larger batch is launched in slices of that many images, with
+// the per-image pointers advanced.
+int ffcv_gather_raw_batch(void *stream, const uint8_t *base, const ffcv_sample *samples, int batch,
+                          uint8_t *out, uint64_t out_stride) {
+  if (batch < 0 || !base || !samples || !out || !out_stride) {
+    ffcv::set_error("ffcv_gather_raw_batch: invalid arguments");
+    return FFCV_EINVAL;
+  }
+  if (batch == 0) return FFCV_OK;
+  unsigned gx = (unsigned)((out_stride + 255) / 256);
+  if (gx > 64) gx = 64;
+  for (int64_t k0 = 0; k0 < batch; k0 += GATHER_MAX_GRID_Y) {
+    const unsigned slice = (unsigned)(batch - k0 < GATHER_MAX_GRID_Y ? batch - k0 : GATHER_MAX_GRID_Y);
+    hipLaunchKernelGGL(gather_raw_kernel, dim3(gx, slice), dim3(256), 0, ffcv::as_stream(stream), base,
+                       samples + k0, out + out_stride * k0, out_stride);
+    FFCV_LAUNCH_CHECK("gather_raw_kernel");
+  }
+  return FFCV_OK;
+}
 
 uint64_t ffcv_gather_rows_cutover(void) { return GATHER_LARGE_BYTES; }
 uint64_t ffcv_gather_rows_subwave(void) { return GATHER_SUBWAVE_BYTES; }

@@ -19,10 +19,6 @@
 // partial 16 bytes of a sample are read and written element by element.  No
 // byte outside [in, in + n * elems) is read and none outside the same range
 // of out written.  Runs of 4 measured best.
-#include <algorithm>
-#include <atomic>
-#include <thread>
-#include <vector>
 
 #include "api_internal.h"
 
@@ -249,8 +245,7 @@ int ffcv_mixup_batch_host(const void *in, void *out, int64_t n_samples, int64_t 
   if (mix_check("ffcv_mixup_batch_host", in, out, n_samples, sample_elems, dtype, batch_size, lam, &bytes))
     return FFCV_EINVAL;
   const uint64_t n = (uint64_t)n_samples, elems = (uint64_t)sample_elems, bs = (uint64_t)batch_size;
-  std::atomic<uint64_t> next{0};
-  auto work = [&]() {
+  ffcv::host_threads(nthreads, n_samples, [&](std::atomic<uint64_t> &next, int, int) {
     for (;;) {
       const uint64_t i = next.fetch_add(1);
       if (i >= n) return;
@@ -262,13 +257,7 @@ int ffcv_mixup_batch_host(const void *in, void *out, int64_t n_samples, int64_t 
       else
         mix_host_sample<float>((const float *)in, (float *)out, elems, i, nb, l);
     }
-  };
-  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(nthreads, n_samples));
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work);
-  work();
-  for (auto &x : th) x.join();
+  });
   return FFCV_OK;
 }
 

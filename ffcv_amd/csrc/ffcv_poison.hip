@@ -22,10 +22,6 @@
 // by element.  No byte outside [images, images + n * elems) is touched.
 // 8 bytes per thread and runs of 64 (shorter on small launches) measured best
 // (DESIGN.md s16).
-#include <algorithm>
-#include <atomic>
-#include <thread>
-#include <vector>
 
 #include "api_internal.h"
 #include "poison_common.h"
@@ -238,8 +234,7 @@ int ffcv_poison_batch_host(uint8_t *images, int64_t n_samples, int64_t sample_el
     return FFCV_EINVAL;
   if (n_poison == 0) return FFCV_OK;
   const uint64_t n = (uint64_t)n_samples, elems = (uint64_t)sample_elems;
-  std::atomic<uint64_t> next{0};
-  auto work = [&]() {
+  ffcv::host_threads(nthreads, n_samples, [&](std::atomic<uint64_t> &next, int, int) {
     for (;;) {
       const uint64_t i = next.fetch_add(1);
       if (i >= n) return;
@@ -247,13 +242,7 @@ int ffcv_poison_batch_host(uint8_t *images, int64_t n_samples, int64_t sample_el
       uint8_t *p = images + i * elems;
       for (uint64_t j = 0; j < elems; j++) p[j] = poison_value(p[j], keep[j], add[j], clamp_lo, clamp_hi);
     }
-  };
-  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(nthreads, n_samples));
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work);
-  work();
-  for (auto &x : th) x.join();
+  });
   return FFCV_OK;
 }
 

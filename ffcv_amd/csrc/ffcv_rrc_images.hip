@@ -10,15 +10,12 @@
 // crop's rows once, builds the out_w + out_h taps in LDS itself and writes the
 // final pixels (rrc_images_kernel).  Images too large for that run the band
 // kernel behind a small descriptor kernel (rrc_images_desc_kernel).
-#include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <thread>
-#include <vector>
 
 #include "api_internal.h"
 #include "device_common.h"
 #include "lds_stage.h"
+#include "resize_out.h"
 
 #define RRCI_THREADS 256
 // The largest staged source (rows of whole 16-byte chunks, see lds_src_bytes)
@@ -26,9 +23,7 @@
 // the measurement in profiles/rrc_transform_bench.txt: the
 // LDS kernel is 1.9-3.5x faster than the band kernel up to a 64 x 64 source
 // and slower from 96 x 96 on.
-#ifndef RRCI_LDS_BYTES
 #define RRCI_LDS_BYTES 16384
-#endif
 #define RRCI_LDS_MAX 65536  // LDS one workgroup may allocate
 #define RRCI_TAP_BYTES 32   // one LDS tap record (AreaTaps: 28 bytes, LinTap: 16)
 
@@ -98,16 +93,8 @@ FFCV_HD int row_chunks(int w) { return lds_chunks(3 * w); }
 // pixel reads' look-ahead (two aligned dwords per pixel: up to 5 bytes past it)
 static uint64_t lds_src_bytes(int H, int W) { return (uint64_t)H * row_chunks(W) * 16 + 16; }
 
-// Crop rows in LDS: row y holds the 16-byte aligned chunks covering crop row
-// y, so its first byte sits at the row's alignment offset (lds_stage.h).
-struct ImgLds {
-  const uint8_t *p;
-  int pitch, lead, stepmod;
-  FFCV_DEV const uint8_t *row(int y) const { return p + y * pitch + ((lead + y * stepmod) & 15); }
-  FFCV_DEV const uint8_t *pix(int y, int x) const { return row(y) + x * 3; }
-  FFCV_DEV uint32_t px(int y, int x) const { return lds_pixel(pix(y, x)); }
-  FFCV_DEV int at(int y, int x, int c) const { return (int)((px(y, x) >> (8 * c)) & 0xffu); }
-};
+// the whole crop's staged rows (resize_out.h, r0 = 0); every read is a pixel's two aligned dwords
+typedef StagedRows<true> ImgLds;
 
 // One workgroup per image.  Dynamic LDS: [staged rows | taps | LUT].
 //   Validation: an invalid crop's image is not read; its output row is
@@ -149,7 +136,7 @@ __global__ void __launch_bounds__(RRCI_THREADS)
   const uint64_t src0 = (uint64_t)(uintptr_t)in + (uint64_t)k * in_stride + ((uint64_t)ci * W + cj) * 3;
   const int nch = row_chunks(cww);
   const int total = chh * nch;  // <= H * row_chunks(W): inside src_cap
-  ImgLds L{(const uint8_t *)s_src, nch * 16, (int)(src0 & 15), (int)(step & 15)};
+  ImgLds L{(const uint8_t *)s_src, nch * 16, (int)(src0 & 15), (int)(step & 15), 0};
   const ResizePlan P = make_plan(cww, chh, out_w, out_h);
   bool first = true;
   for (int b0 = t; b0 < total || first; b0 += 4 * RRCI_THREADS) {
@@ -194,6 +181,8 @@ __global__ void __launch_bounds__(RRCI_THREADS)
   }
   __syncthreads();
 
+  // (in place: through make_epilogue this kernel grew by ten scalar instructions and its large
+  // LDS-regime cases measured up to 0.7 % slower, profiles/rrc_split_ab.txt)
   Epilogue ep;
   ep.out_h = out_h;
   ep.out_w = out_w;
@@ -245,26 +234,7 @@ __global__ void __launch_bounds__(RRCI_THREADS)
 
   const bool wide = (out_w & 3) == 0 && ((((uintptr_t)out) | stride) & (FP16 ? 7 : 3)) == 0;
   if (wide) {
-    // four adjacent pixels as one 12-byte (u8) or three 8-byte (fp16) stores
-    auto put = [&](int dy, int dx0, const int v[12]) {
-      const uint64_t px = (uint64_t)dy * out_w + dx0;
-      if (FP16) {  // 24-byte group, 8-byte aligned (dx0 % 4 == 0)
-        uint32_t h[12];
-#pragma unroll
-        for (int e = 0; e < 12; e++) h[e] = s_lut[v[e] * 3 + e % 3];
-        uint2 *o64 = (uint2 *)((uint16_t *)o + px * 3);
-        o64[0] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-        o64[1] = make_uint2(h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-        o64[2] = make_uint2(h[8] | (h[9] << 16), h[10] | (h[11] << 16));
-      } else {  // 12-byte group, 4-byte aligned
-        typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-        u32x3 w;
-        w.x = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-        w.y = v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24);
-        w.z = v[8] | (v[9] << 8) | (v[10] << 16) | (v[11] << 24);
-        __builtin_nontemporal_store(w, (u32x3 *)((uint8_t *)o + px * 3));
-      }
-    };
+    // four adjacent pixels as one 12-byte (u8) or three 8-byte (fp16) stores (store_quad)
     const int nq = out_w >> 2;
     if (P.kind == 3 && nq <= RRCI_THREADS) {
       // Linear walk (resize_linear in its separable form, as resize.cpp runs
@@ -336,7 +306,7 @@ __global__ void __launch_bounds__(RRCI_THREADS)
             v[3 * j + c] = cutpx ? (int)ep.fill[c] : r;
           }
         }
-        put(dy, dx0, v);
+        store_quad<FP16>(o, (uint64_t)dy * out_w + dx0, v, s_lut);
       }
       return;
     }
@@ -346,7 +316,7 @@ __global__ void __launch_bounds__(RRCI_THREADS)
       int v[12];
 #pragma unroll
       for (int j = 0; j < 4; j++) pixel(dy, dx0 + j, v + 3 * j);
-      put(dy, dx0, v);
+      store_quad<FP16>(o, (uint64_t)dy * out_w + dx0, v, s_lut);
     }
     return;
   }
@@ -355,17 +325,7 @@ __global__ void __launch_bounds__(RRCI_THREADS)
     const int dy = i / out_w, dx = i - dy * out_w;
     int v[3];
     pixel(dy, dx, v);
-    if (FP16) {
-      uint16_t *q = (uint16_t *)o + (uint64_t)i * 3;
-      q[0] = s_lut[v[0] * 3 + 0];
-      q[1] = s_lut[v[1] * 3 + 1];
-      q[2] = s_lut[v[2] * 3 + 2];
-    } else {
-      uint8_t *q = (uint8_t *)o + (uint64_t)i * 3;
-      q[0] = (uint8_t)v[0];
-      q[1] = (uint8_t)v[1];
-      q[2] = (uint8_t)v[2];
-    }
+    store_px<FP16>(o, (uint64_t)i, v, s_lut);
   }
 }
 
@@ -596,9 +556,8 @@ int ffcv_rrc_images_batch_host(const uint8_t *in, uint64_t in_stride, int batch,
       return FFCV_EINVAL;
     }
   }
-  std::atomic<int> next{0};
-  auto work = [&]() {
-    for (int k = next.fetch_add(1); k < batch; k = next.fetch_add(1)) {
+  ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
+    for (int k = (int)next.fetch_add(1); k < batch; k = (int)next.fetch_add(1)) {
       const int32_t *c = crops + 4 * k;
       uint8_t *dst = out + (uint64_t)k * stride;
       if (!crop_ok(c[0], c[1], c[2], c[3], height, width)) {
@@ -610,13 +569,7 @@ int ffcv_rrc_images_batch_host(const uint8_t *in, uint64_t in_stride, int batch,
              (int64_t)c[1] + c[3], (int64_t)(uintptr_t)dst, out_h, out_w);
       if (status) status[k] = FFCV_SAMPLE_OK;
     }
-  };
-  const int T = std::max(1, std::min(nthreads, batch));
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work);
-  work();
-  for (auto &x : th) x.join();
+  });
   return FFCV_OK;
 }
 

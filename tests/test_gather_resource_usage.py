@@ -8,8 +8,11 @@ As written the compiler reports, for gfx950:
   gather_rows_kernel<16>   (16 lanes per row)   20 VGPRs, 8 waves/SIMD
   gather_rows_kernel<64>   (a wave per row)     20 VGPRs, 8 waves/SIMD
   gather_rows_grid_kernel  (2-D grid)           68 VGPRs, 7 waves/SIMD
+  gather_raw_kernel        (raw sample bytes)    5 VGPRs, 8 waves/SIMD
+  gather_samples_kernel    (descriptors)        12 VGPRs, 8 waves/SIMD
 
-(the grid kernel holds four vectors of five dwords per lane in flight).  Each
+(the grid kernel holds four vectors of five dwords per lane in flight; the
+last two are the decoders' simple gathers).  Each
 kernel is pinned to its count, so that a change that costs registers or
 occupancy fails here; one that saves some lowers the bound.
 """
@@ -22,6 +25,8 @@ BUDGET = {
     'gather_rows_kernelILi16E': (20, 8),
     'gather_rows_kernelILi64E': (20, 8),
     'gather_rows_grid_kernel': (68, 7),
+    'gather_raw_kernel': (5, 8),
+    'gather_samples_kernel': (12, 8),
 }
 
 
@@ -33,7 +38,7 @@ def usage():
 
 
 def test_every_gather_kernel_is_reported(usage):
-    kernels = [k for k in usage if 'gather_rows' in k]
+    kernels = [k for k in usage if 'gather_' in k]
     assert len(kernels) == len(BUDGET) == len(usage), sorted(usage)
     for frag in BUDGET:
         assert sum(frag in k for k in kernels) == 1, (frag, kernels)

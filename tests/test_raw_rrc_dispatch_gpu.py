@@ -186,8 +186,19 @@ def groups_last_byte():
             Group((17, 32), first + [Item(60, 700, (20, 50, 40, 650))], tail=0, what='last')]
 
 
+# ---- 11. one cutout across each quad walk: out 20 x 16 (3 * 16 % 16 == 0: the linear quad walk; 20 rows: two
+# bands), a square of 5 at (y 13, x 6): rows 13..17 span the band boundary at row 16, columns 6..10 the quad
+# boundary at column 8 (flipped with cut-before-flip: columns 5..9).  Crop 10 x 9 is kind 3 (the linear walk),
+# 30 x 24 has both scales 1.5 (the area walk), 50 x 40 both 2.5 (the general-area quads: a band reads 40
+# source rows of (3 * 40 + 30) >> 4 = 9 chunks, 5,760 bytes: staged).
+def groups_cutout_across_walks():
+    items = [_item(n, h, w, flip=f, cut=(13, 6)) for n, (h, w) in enumerate(((10, 9), (30, 24), (50, 40)))
+             for f in (0, 1)]
+    return [Group((20, 16), items, cs=5, cbf=cbf, flips=True, what='cutwalk') for cbf in (False, True)]
+
+
 ALL = [groups_widths, groups_quads, groups_thread_groups, groups_staging, groups_row_walk, groups_area,
-       groups_epilogue, groups_stride, groups_mixed, groups_last_byte]
+       groups_epilogue, groups_stride, groups_mixed, groups_last_byte, groups_cutout_across_walks]
 
 
 def _tpg(ow):
@@ -246,6 +257,12 @@ def test_coverage_table():
             for flip in (0, 1):
                 assert has(w4=w4, cbf=cbf, flip=flip, cs=1) and has(w4=w4, cbf=cbf, flip=flip, cs=lambda c: c > 6)
                 assert has(w4=w4, cbf=cbf, flip=flip, cs=6, cut=lambda c: c[1] % 4 in (1, 2, 3))
+    # each quad walk with a cutout that crosses a band and a quad boundary
+    for cbf in (False, True):
+        for flip in (0, 1):
+            for walk in (dict(kind=3), dict(kind=2, walk=True), dict(kind=2, walk=False)):
+                assert has(what='cutwalk', cbf=cbf, flip=flip, v16=0, oh=lambda h: h > 16, cs=5,
+                           cut=lambda c: c[0] < 16 < c[0] + 5 and c[1] < 8 < c[1] + 5, **walk), (cbf, flip, walk)
     # every source is small
     assert max(r['sh'] * r['sw'] * 3 for r in rec) <= 160_000
     # the alignment groups: every row lead (first crop byte's address mod 16, the buffer being 16-byte
@@ -416,3 +433,8 @@ def test_non_raw_sample_in_raw_batch(hip_lib, oracle):
 @gpu
 def test_crop_ends_on_last_byte(hip_lib, oracle):
     _run(hip_lib, oracle, groups_last_byte, 10)
+
+
+@gpu
+def test_cutout_across_bands_and_quads_in_each_walk(hip_lib, oracle):
+    _run(hip_lib, oracle, groups_cutout_across_walks, 11)

@@ -148,6 +148,36 @@ def test_abi_both_regimes(hip_lib, oracle, lut_dev, src, B):
     assert (whole[:GUARD + 1] == 0xEE).all() and (whole[-GUARD:] == 0xEE).all()
 
 
+def test_cutout_across_quads_in_the_lds_regime(hip_lib, oracle, lut_dev):
+    """The raw dispatch test's cutout group through the image kernel: 52 x 44
+    images (staged source 52 * ((3 * 44 + 30) >> 4) * 16 + 16 = 8,336 bytes: the
+    LDS regime), out 20 x 16, crops 10 x 9 (linear walk), 30 x 24 (area, scales
+    1.5) and 50 x 40 (area, scales 2.5), a cutout of 5 at (y 13, x 6) that cuts
+    through the quads of columns 4..7 and 8..11, flip 0 and 1, cut before and
+    after the flip, u8 and fp16 with the group stores (aligned strides)."""
+    from ffcv_amd import libffcv as L
+    H, W, oh, ow, cut = 52, 44, 20, 16, 5
+    crops = np.array([c for c in ((1, 2, 10, 9), (3, 4, 30, 24), (1, 2, 50, 40)) for _ in (0, 1)], np.int32)
+    B = len(crops)
+    assert kinds(crops, oh, ow) == {2, 3}
+    flips = np.array([0, 1] * 3, np.uint8)
+    cyx = np.tile(np.array([[13, 6]], np.int32), (B, 1))
+    imgs = np.random.default_rng(11).integers(0, 256, (B, H, W, 3), dtype=np.uint8)
+    view, whole = guarded(imgs)
+    want, _ = expected_resize(oracle, imgs, crops, oh, ow)
+    for cbf in (False, True):
+        w8 = expected_epilogue(want, flips, cyx, cut, FILL, cbf)
+        got, st, gaps, nws = run_images(L, view, B, H, W, crops, oh, ow, None, flips, cyx, cut, cbf, pad=4)
+        assert nws == 0, nws
+        assert np.array_equal(got, w8), (cbf, np.argwhere((got != w8).any(axis=(1, 2, 3))).ravel())
+        assert (st == SAMPLE_OK).all() and (gaps == 0xAB).all()
+        w16 = expected_epilogue(want, flips, cyx, cut, FILL, cbf, LUT).view(np.uint16)
+        got, st, gaps, _ = run_images(L, view, B, H, W, crops, oh, ow, lut_dev, flips, cyx, cut, cbf, pad=8)
+        assert np.array_equal(got, w16), (cbf, np.argwhere((got != w16).any(axis=(1, 2, 3))).ravel())
+        assert (st == SAMPLE_OK).all() and (gaps == 0xAB).all()
+    assert (whole[:GUARD + 1] == 0xEE).all() and (whole[-GUARD:] == 0xEE).all()
+
+
 def test_every_crop_size_of_32(hip_lib, oracle):
     """A window of every size of a 32 x 32 source to 32 x 32 (1,024 images in
     one launch): every linear tap pattern, the copy among them."""
