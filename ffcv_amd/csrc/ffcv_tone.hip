@@ -50,13 +50,14 @@ __global__ void __launch_bounds__(64) tone_draw_kernel(const uint64_t *__restric
   if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
 }
 
-// prog: steps[i] in byte i, n of them.  img / npx: bytes / pixels of one image;
+// prog: steps[i] in byte i, n of them; bits_k: posterize's bits per image, or
+// NULL for bits_all.  img / npx: bytes / pixels of one image;
 // tile_px pixels per workgroup (tile_px * 3 <= TONE_LDS_BYTES), ntiles
 // workgroups per image.  ws: 3 x 256 counters per image (tiles with statistics).
 __global__ void __launch_bounds__(TONE_THREADS)
-    tone_kernel(uint8_t *__restrict__ images, int B, uint64_t img, uint32_t npx, uint32_t prog, int n, int bits,
-                const uint8_t *__restrict__ apply, uint32_t *__restrict__ ws, int mode, uint32_t tile_px,
-                uint32_t ntiles) {
+    tone_kernel(uint8_t *__restrict__ images, int B, uint64_t img, uint32_t npx, uint32_t prog, int n, int bits_all,
+                const uint8_t *__restrict__ bits_k, const uint8_t *__restrict__ apply, uint32_t *__restrict__ ws,
+                int mode, uint32_t tile_px, uint32_t ntiles) {
   typedef uint32_t tx4_t __attribute__((ext_vector_type(4)));
   __shared__ tx4_t s_img[TONE_LDS_BYTES / 16 + 2];  // + the range's lead bytes
   __shared__ uint32_t s_hist[3 * 256];              // the channel histograms as the current step finds them
@@ -76,6 +77,8 @@ __global__ void __launch_bounds__(TONE_THREADS)
     if (tone_needs_stats((int)((prog >> (8 * i)) & 0xffu))) last_stat = i;
   }
   if (!applied) return;  // an image no step touches is neither read nor written
+  // posterize's bits: the image's own (one scalar load, kept inside 1 .. 8) or the program's
+  const int bits = bits_k ? min(8, max(1, (int)bits_k[k])) : bits_all;
   const bool hist = last_stat >= 0;
   if (mode == TONE_HIST && !hist) return;
   uint32_t *wsk = ws + (uint64_t)k * 768u;
@@ -312,11 +315,13 @@ int ffcv_tone_draw_batch_host(const uint64_t *sample_ids, int batch, uint64_t lo
 uint64_t ffcv_tone_workspace_bytes(int batch) { return batch > 0 ? 3072ull * (uint64_t)batch : 0; }
 uint64_t ffcv_tone_lds_bytes(void) { return TONE_LDS_BYTES; }
 
-int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height, int width, const ffcv_tone_params *params,
-                    const uint8_t *apply, void *workspace, uint64_t workspace_bytes) {
-  if (!ffcv::u8_images_ok("ffcv_tone_batch", images && params && apply, batch, height, width)) return FFCV_EINVAL;
+// both device entries; bits: per image or NULL
+static int tone_batch(const char *who, void *stream, uint8_t *images, int batch, int height, int width,
+                      const ffcv_tone_params *params, const uint8_t *apply, void *workspace,
+                      uint64_t workspace_bytes, const uint8_t *bits) {
+  if (!ffcv::u8_images_ok(who, images && params && apply, batch, height, width)) return FFCV_EINVAL;
   bool stats = false;
-  if (tone_check_program("ffcv_tone_batch", params, &stats)) return FFCV_EINVAL;
+  if (tone_check_program(who, params, &stats)) return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
   const int n = params->n_steps;
   uint32_t prog = 0;
@@ -325,39 +330,59 @@ int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height, int wi
   const bool whole = img <= TONE_LDS_BYTES;
   uint32_t tile_px, ntiles;
   unsigned blocks;
-  if (!ffcv::run_tiling("ffcv_tone_batch", batch, npx, TONE_LDS_BYTES, TONE_TILE_PX, &tile_px, &ntiles, &blocks))
+  if (!ffcv::run_tiling(who, batch, npx, TONE_LDS_BYTES, TONE_TILE_PX, &tile_px, &ntiles, &blocks))
     return FFCV_EINVAL;
   hipStream_t s = ffcv::as_stream(stream);
   uint32_t *ws = (uint32_t *)workspace;
   if (whole || !stats) {
     hipLaunchKernelGGL(tone_kernel, dim3(blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx, prog, n,
-                       (int)params->bits, apply, ws, whole ? TONE_WHOLE : TONE_MAP, tile_px, ntiles);
+                       (int)params->bits, bits, apply, ws, whole ? TONE_WHOLE : TONE_MAP, tile_px, ntiles);
     FFCV_LAUNCH_CHECK("tone_kernel");
     return FFCV_OK;
   }
   if (!workspace || ((uintptr_t)workspace & 3) || workspace_bytes < ffcv_tone_workspace_bytes(batch)) {
-    ffcv::set_error("ffcv_tone_batch: an autocontrast or equalize step on %dx%d images needs a 4-byte aligned "
+    ffcv::set_error("%s: an autocontrast or equalize step on %dx%d images needs a 4-byte aligned "
                     "workspace of %llu bytes, got %llu",
-                    height, width, (unsigned long long)ffcv_tone_workspace_bytes(batch),
+                    who, height, width, (unsigned long long)ffcv_tone_workspace_bytes(batch),
                     (unsigned long long)workspace_bytes);
     return FFCV_EINVAL;
   }
   FFCV_HIP_CHECK(hipMemsetAsync(workspace, 0, ffcv_tone_workspace_bytes(batch), s));
   hipLaunchKernelGGL(tone_kernel, dim3(blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx, prog, n,
-                     (int)params->bits, apply, ws, TONE_HIST, tile_px, ntiles);
+                     (int)params->bits, bits, apply, ws, TONE_HIST, tile_px, ntiles);
   FFCV_LAUNCH_CHECK("tone_kernel (pass A)");
   hipLaunchKernelGGL(tone_kernel, dim3(blocks), dim3(TONE_THREADS), 0, s, images, batch, img, (uint32_t)npx, prog, n,
-                     (int)params->bits, apply, ws, TONE_MAP, tile_px, ntiles);
+                     (int)params->bits, bits, apply, ws, TONE_MAP, tile_px, ntiles);
   FFCV_LAUNCH_CHECK("tone_kernel (pass B)");
   return FFCV_OK;
 }
 
-int ffcv_tone_batch_host(uint8_t *images, int batch, int height, int width, const ffcv_tone_params *params,
-                         const uint8_t *apply) {
-  if (!ffcv::u8_images_ok("ffcv_tone_batch_host", images && params && apply, batch, height, width))
-    return FFCV_EINVAL;
+int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height, int width, const ffcv_tone_params *params,
+                    const uint8_t *apply, void *workspace, uint64_t workspace_bytes) {
+  return tone_batch("ffcv_tone_batch", stream, images, batch, height, width, params, apply, workspace,
+                    workspace_bytes, NULL);
+}
+
+int ffcv_tone_batch_bits(void *stream, uint8_t *images, int batch, int height, int width,
+                         const ffcv_tone_params *params, const uint8_t *apply, void *workspace,
+                         uint64_t workspace_bytes, const uint8_t *bits) {
+  return tone_batch("ffcv_tone_batch_bits", stream, images, batch, height, width, params, apply, workspace,
+                    workspace_bytes, bits);
+}
+
+// both host entries; bits: per image (each in 1 .. 8 where the program posterizes) or NULL
+static int tone_batch_host(const char *who, uint8_t *images, int batch, int height, int width,
+                           const ffcv_tone_params *params, const uint8_t *apply, const uint8_t *bits) {
+  if (!ffcv::u8_images_ok(who, images && params && apply, batch, height, width)) return FFCV_EINVAL;
   bool stats = false;
-  if (tone_check_program("ffcv_tone_batch_host", params, &stats)) return FFCV_EINVAL;
+  if (tone_check_program(who, params, &stats)) return FFCV_EINVAL;
+  if (bits)
+    for (int i = 0; i < params->n_steps; i++)
+      for (int k = 0; params->steps[i] == FFCV_TONE_POSTERIZE && k < batch; k++)
+        if (bits[k] < 1 || bits[k] > 8) {
+          ffcv::set_error("%s: posterize keeps 1 to 8 bits, got %d for image %d", who, (int)bits[k], k);
+          return FFCV_EINVAL;
+        }
   const uint64_t npx = (uint64_t)height * width;
   const int n = params->n_steps;
   for (int k = 0; k < batch; k++) {
@@ -384,7 +409,7 @@ int ffcv_tone_batch_host(uint8_t *images, int batch, int height, int width, cons
     for (int i = 0; i <= last; i++) {
       if (!apply[(uint64_t)i * batch + k]) continue;
       for (int c = 0; c < 3; c++) {
-        tone_table_host(params->steps[i], params->bits, (uint32_t)npx, h[c], T);
+        tone_table_host(params->steps[i], bits ? (int)bits[k] : (int)params->bits, (uint32_t)npx, h[c], T);
         for (int v = 0; v < 256; v++) comp[c][v] = T[comp[c][v]];
         if (i < last_stat) {
           for (int v = 0; v < 256; v++) h2[c][v] = 0;
@@ -397,6 +422,16 @@ int ffcv_tone_batch_host(uint8_t *images, int batch, int height, int width, cons
       for (int c = 0; c < 3; c++) im[3 * q + c] = comp[c][im[3 * q + c]];
   }
   return FFCV_OK;
+}
+
+int ffcv_tone_batch_host(uint8_t *images, int batch, int height, int width, const ffcv_tone_params *params,
+                         const uint8_t *apply) {
+  return tone_batch_host("ffcv_tone_batch_host", images, batch, height, width, params, apply, NULL);
+}
+
+int ffcv_tone_batch_bits_host(uint8_t *images, int batch, int height, int width, const ffcv_tone_params *params,
+                              const uint8_t *apply, const uint8_t *bits) {
+  return tone_batch_host("ffcv_tone_batch_bits_host", images, batch, height, width, params, apply, bits);
 }
 
 int ffcv_tone_tables_host(int kind, int bits, const uint32_t *hists, uint8_t *tables, int n) {

@@ -187,6 +187,24 @@ _SIGS = {
     'ffcv_gaussian_blur_lds_bytes': (c_uint64, []),
     'ffcv_gaussian_blur_band_rows': (c_uint64, []),
     'ffcv_gaussian_blur_strip_cols': (c_uint64, [c_int, c_int, c_int]),
+    'ffcv_sharpness_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_double,
+                                          c_void_p, c_void_p, c_void_p]),
+    'ffcv_sharpness_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_void_p,
+                                               c_void_p]),
+    'ffcv_sharpness_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_uint64]),
+    'ffcv_sharpness_batch_host': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_uint64,
+                                          c_int]),
+    'ffcv_tone_batch_bits': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_uint64,
+                                     c_void_p]),
+    'ffcv_tone_batch_bits_host': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'ffcv_policy_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_void_p, c_int, c_int] +
+                               [c_void_p] * 10),
+    'ffcv_policy_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_void_p, c_int, c_int] +
+                                    [c_void_p] * 9),
+    'ffcv_sharpness_lds_bytes': (c_uint64, []),
+    'ffcv_sharpness_band_rows': (c_uint64, []),
+    'ffcv_sharpness_strip_cols': (c_uint64, [c_int, c_int]),
     'ffcv_hue_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_void_p,
                                     c_void_p, c_void_p]),
     'ffcv_hue_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_void_p,
@@ -860,6 +878,71 @@ def gaussian_blur_batch_host(src: np.ndarray, dst: np.ndarray, ksize, apply, wei
     return dst[:B]
 
 
+def sharpness_draw_batch(ids, loader_seed, epoch, p, factor, apply, factor_out, status=None, stream=None):
+    """RandomAdjustSharpness's draws of the batch on the device (op id 19):
+    apply uint8[B] = rand() < p, factor_out float32[B] = the constant."""
+    _check(lib().ffcv_sharpness_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]), _seed64(loader_seed),
+                                           int(epoch), float(p), float(factor), _p(apply), _p(factor_out),
+                                           _p(status)), 'ffcv_sharpness_draw_batch')
+
+
+def sharpness_draw_batch_host(ids, loader_seed, epoch, p, factor):
+    """The same draws on the host: (apply uint8 (B,), factor float32 (B,))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    apply = np.empty(ids.size, np.uint8)
+    factor_out = np.empty(ids.size, np.float32)
+    _check(lib().ffcv_sharpness_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch), float(p),
+                                                float(factor), _p(apply), _p(factor_out)),
+           'ffcv_sharpness_draw_batch_host')
+    return apply, factor_out
+
+
+def sharpness_lds_bytes():
+    """6 * H * W of the largest image one workgroup of sharpness_batch takes whole."""
+    return int(lib().ffcv_sharpness_lds_bytes())
+
+
+def sharpness_band_rows():
+    """Output rows per workgroup beyond the whole-image regime."""
+    return int(lib().ffcv_sharpness_band_rows())
+
+
+def sharpness_strip_cols(height, width):
+    """Output columns per workgroup (== width while one strip serves a band)."""
+    return int(lib().ffcv_sharpness_strip_cols(int(height), int(width)))
+
+
+def sharpness_batch(src, dst, apply, factor, dst_stride=0, stream=None):
+    """Per image of a dense device uint8 (B, H, W, 3) batch: copy (apply[k] ==
+    0), sharpen with factor[k] (1) or leave ``dst`` alone (2)
+    (ffcv_sharpness_batch): one launch, out of place; apply device uint8 (B,),
+    factor device float32 (B,)."""
+    if src.dim() != 4 or int(src.shape[3]) != 3 or src.element_size() != 1 or not src.is_contiguous():
+        raise TypeError('sharpness_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
+    B, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    _check(lib().ffcv_sharpness_batch(_stream(stream), _p(src), _p(dst), B, H, W, _p(apply), _p(factor),
+                                      int(dst_stride)), 'ffcv_sharpness_batch')
+    return dst
+
+
+def sharpness_batch_host(src: np.ndarray, dst: np.ndarray, apply, factor, nthreads=1):
+    """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
+    if not (isinstance(src, np.ndarray) and isinstance(dst, np.ndarray) and src.dtype == np.uint8 and
+            dst.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3 and src.flags.c_contiguous and
+            dst.flags.c_contiguous and dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
+        raise TypeError('sharpness_batch_host: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are '
+                        'required')
+    B, H, W = (int(x) for x in src.shape[:3])
+    apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
+    factor = np.ascontiguousarray(factor, np.float32).reshape(-1)
+    if apply.size != B or factor.size != B:
+        raise TypeError(f'sharpness_batch_host: apply ({B},) and factor ({B},) are required, got '
+                        f'{apply.shape} and {factor.shape}')
+    _check(lib().ffcv_sharpness_batch_host(_p(src), _p(dst), B, H, W, _p(apply), _p(factor), 0,
+                                           int(max(1, nthreads))), 'ffcv_sharpness_batch_host')
+    return dst[:B]
+
+
 def hue_draw_batch(ids, loader_seed, epoch, p, magnitude, apply, shift, status=None, stream=None):
     """RandomHue's decisions of the batch on the device (op id 12): apply
     uint8[B], shift float64[B] = uniform(-magnitude, magnitude)."""
@@ -1004,6 +1087,64 @@ def tone_batch_host(images, steps, bits, apply):
     apply = np.ascontiguousarray(apply, np.uint8).reshape(max(params.n_steps, 1), B)
     _check(lib().ffcv_tone_batch_host(_p(images), B, H, W, ctypes.byref(params), _p(apply)), 'ffcv_tone_batch_host')
     return images
+
+
+def tone_batch_bits(images, steps, apply, bits, workspace=None, stream=None):
+    """tone_batch with posterize's bits per image: bits device uint8 (B,)
+    (ffcv_tone_batch_bits)."""
+    B, H, W = _u8_batch_dims(images, 'tone_batch_bits')
+    params = steps if isinstance(steps, ToneParams) else tone_params(steps, 8)
+    wb = int(workspace.numel() * workspace.element_size()) if workspace is not None else 0
+    _check(lib().ffcv_tone_batch_bits(_stream(stream), _p(images), B, H, W, ctypes.byref(params), _p(apply),
+                                      _p(workspace), wb, _p(bits)), 'ffcv_tone_batch_bits')
+
+
+def tone_batch_bits_host(images, steps, apply, bits):
+    """The same in place on a C-contiguous numpy uint8 (B, H, W, 3); bits uint8 (B,)."""
+    B, H, W = _u8_batch_dims(images, 'tone_batch_bits_host')
+    params = steps if isinstance(steps, ToneParams) else tone_params(steps, 8)
+    apply = np.ascontiguousarray(apply, np.uint8).reshape(max(params.n_steps, 1), B)
+    bits = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+    if bits.size != B:
+        raise TypeError(f'tone_batch_bits_host: bits ({B},) is required, got {bits.shape}')
+    _check(lib().ffcv_tone_batch_bits_host(_p(images), B, H, W, ctypes.byref(params), _p(apply), _p(bits)),
+           'ffcv_tone_batch_bits_host')
+    return images
+
+
+POLICY_NOPS = 14  # operations of the TrivialAugmentWide policy, rows of its value table
+# the arrays ffcv_policy_draw_batch fills, in argument order: (name, dtype, shape per batch size B)
+POLICY_ARRAYS = (('op', np.uint8, lambda B: (B,)), ('cj_apply', np.uint8, lambda B: (4, B)),
+                 ('cj_ratio', np.float64, lambda B: (4, B)), ('tone_apply', np.uint8, lambda B: (3, B)),
+                 ('tone_bits', np.uint8, lambda B: (B,)), ('aff_apply', np.uint8, lambda B: (B,)),
+                 ('aff_coef', np.int64, lambda B: (B, 6)), ('sharp_apply', np.uint8, lambda B: (B,)),
+                 ('sharp_factor', np.float32, lambda B: (B,)))
+
+
+def policy_draw_batch(ids, loader_seed, epoch, nbins, table, height, width, out, status=None, stream=None):
+    """TrivialAugmentWide's draws of the batch on the device (op id 20) into
+    the device tensors ``out[name]`` of POLICY_ARRAYS; table: device float64
+    (14, nbins)."""
+    if table.numel() != POLICY_NOPS * int(nbins) or table.element_size() != 8 or not table.is_contiguous():
+        raise TypeError(f'policy_draw_batch: a contiguous float64 ({POLICY_NOPS}, {nbins}) table is required')
+    _check(lib().ffcv_policy_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]), _seed64(loader_seed), int(epoch),
+                                        int(nbins), _p(table), int(height), int(width),
+                                        *[_p(out[name]) for name, _, _ in POLICY_ARRAYS], _p(status)),
+           'ffcv_policy_draw_batch')
+
+
+def policy_draw_batch_host(ids, loader_seed, epoch, nbins, table, height, width):
+    """The same draws on the host: a dict of the POLICY_ARRAYS."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.shape != (POLICY_NOPS, int(nbins)):
+        raise TypeError(f'policy_draw_batch_host: a float64 ({POLICY_NOPS}, {nbins}) table is required')
+    out = {name: np.empty(shape(ids.size), dt) for name, dt, shape in POLICY_ARRAYS}
+    _check(lib().ffcv_policy_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch), int(nbins),
+                                             _p(table), int(height), int(width),
+                                             *[_p(out[name]) for name, _, _ in POLICY_ARRAYS]),
+           'ffcv_policy_draw_batch_host')
+    return out
 
 
 def tone_tables_host(kind, bits, hists):

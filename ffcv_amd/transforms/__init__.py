@@ -5,6 +5,8 @@ from .random_resized_crop import RandomResizedCrop
 from .color_jitter import (RandomBrightness, RandomContrast, RandomSaturation, RandomGrayscale,
                            RandomSolarization)
 from .gaussian_blur import GaussianBlur
+from .sharpness import RandomAdjustSharpness
+from .auto_augment import TrivialAugmentWide
 from .hue import RandomHue, RandomColorJitter
 from .affine import RandomAffine, RandomRotation
 from .tone import RandomPosterize, RandomAutocontrast, RandomEqualize, RandomInvert
@@ -19,7 +21,8 @@ from .common import Squeeze
 __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 'Squeeze', 'View',
            'RandomResizedCrop', 'RandomHorizontalFlip', 'RandomTranslate', 'Cutout', 'ModuleWrapper',
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
-           'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomHue', 'RandomColorJitter',
-           'RandomAffine', 'RandomRotation',
+           'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomAdjustSharpness', 'RandomHue',
+           'RandomColorJitter',
+           'RandomAffine', 'RandomRotation', 'TrivialAugmentWide',
            'RandomPosterize', 'RandomAutocontrast', 'RandomEqualize', 'RandomInvert',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']

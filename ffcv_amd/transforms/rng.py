@@ -9,8 +9,9 @@ its own id, so that a pipeline with a crop decoder and the transform does not
 draw the same stream twice), 9 grayscale, 10 solarization, 11 blur, 12 hue,
 13 joint colour jitter (RandomColorJitter: five draws from one stream),
 14 affine (RandomAffine and RandomRotation: seven draws from one stream),
-15 posterize, 16 autocontrast, 17 equalize, 18 invert (one draw each).  The
-device kernels use the same function
+15 posterize, 16 autocontrast, 17 equalize, 18 invert, 19 sharpness
+(RandomAdjustSharpness) (one draw each), 20 policy (TrivialAugmentWide: three
+draws from one stream).  The device kernels use the same function
 (csrc/device_common.h sample_seed).  The reference itself draws from numba's
 per-thread generators seeded from OS entropy (nondeterministic); see
 DESIGN.md "RNG contract".

@@ -700,6 +700,65 @@ uint64_t ffcv_gaussian_blur_lds_bytes(void);
 uint64_t ffcv_gaussian_blur_band_rows(void);
 uint64_t ffcv_gaussian_blur_strip_cols(int height, int width, int ksize);
 
+/* ------------------------------------------- RandomAdjustSharpness ----- */
+/* RandomAdjustSharpness (the reference has none, the semantics
+ * are Pillow's ImageEnhance.Sharpness restated in float32).  Seeding contract
+ * op id 19: one draw per sample, apply = rand() < p.
+ *   p in [0, 1];  factor finite in [0, 16]
+ *   apply : uint8[B], 0 or 1;  factor_out : float32[B], float32(factor)
+ *   status : int32[B] or NULL (device entry only) */
+int ffcv_sharpness_draw_batch(void *stream, const uint64_t *sample_ids,
+                              int batch, uint64_t loader_seed, uint64_t epoch,
+                              double p, double factor, uint8_t *apply,
+                              float *factor_out, int32_t *status);
+int ffcv_sharpness_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                   uint64_t loader_seed, uint64_t epoch,
+                                   double p, double factor, uint8_t *apply,
+                                   float *factor_out);
+
+/* Sharpness of a dense device [B][height][width][3] uint8 batch, out of
+ * place, in ONE launch; image k is written at dst + k * dst_stride_bytes (0 =
+ * dense).  apply[k] selects per image:
+ *   1 : sharpen with a = factor[k];
+ *   2 : leave dst alone (nothing of image k is read or written);
+ *   0 and every other value : copy src to dst.
+ * All arithmetic is float32, every product, difference and sum rounded on its
+ * own (never fused).  With w = 1/13, w5 = 5/13 (float32 quotients) and v the
+ * bytes of a channel, for a byte i = v(y, x) inside the outermost ring of an
+ * image of at least 3 x 3:
+ *   row(y') = (w v(y', x - 1) + wc v(y', x)) + w v(y', x + 1)
+ *             (wc = w5 on the centre row, w elsewhere)
+ *   s = ((0.5 + row(y - 1)) + row(y)) + row(y + 1)
+ *   d = float(int(clamp(s, 0, 255)))
+ *   out = uint8(clamp(d + a (i - d), 0, 255))         (truncation)
+ * and d = i on the outermost ring and in images below 3 x 3, which therefore
+ * come out unchanged.  factor[k] must be finite where apply[k] == 1.
+ * Any byte alignment of src and dst; loads are 16-byte aligned chunks holding
+ * at least one byte of an image (the rule of ffcv_gather_rows).
+ * Two regimes: while 6 * height * width <= ffcv_sharpness_lds_bytes() a
+ * workgroup owns an image; larger images are cut into bands of
+ * ffcv_sharpness_band_rows() rows, and a band too wide for a workgroup's LDS
+ * into column strips of ffcv_sharpness_strip_cols(height, width) columns (==
+ * width while one strip serves).  Supported sizes: height and width up to
+ * 65535.
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, sizes <= 0 or
+ * beyond 65535, a dst_stride_bytes smaller than an image, src and dst ranges
+ * that overlap (dst == src included), or more workgroups than one launch
+ * takes. */
+int ffcv_sharpness_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                         int batch, int height, int width,
+                         const uint8_t *apply, const float *factor,
+                         uint64_t dst_stride_bytes);
+/* The same on host memory over nthreads threads, compiled from the kernel's
+ * pixel functions (csrc/sharpness_common.h). */
+int ffcv_sharpness_batch_host(const uint8_t *src, uint8_t *dst, int batch,
+                              int height, int width, const uint8_t *apply,
+                              const float *factor, uint64_t dst_stride_bytes,
+                              int nthreads);
+uint64_t ffcv_sharpness_lds_bytes(void);
+uint64_t ffcv_sharpness_band_rows(void);
+uint64_t ffcv_sharpness_strip_cols(int height, int width);
+
 /* ------------------------------- hue, jointly gated colour jitter ----- */
 /* RandomHue and RandomColorJitter (the reference has neither,
  * the semantics are this project's own).  Seeding contract op ids: 12 hue,
@@ -1007,10 +1066,79 @@ int ffcv_tone_batch(void *stream, uint8_t *images, int batch, int height,
  * the kernels (csrc/tone_common.h) and composed the same way. */
 int ffcv_tone_batch_host(uint8_t *images, int batch, int height, int width,
                          const ffcv_tone_params *params, const uint8_t *apply);
+/* ffcv_tone_batch with posterize's bits per image: bits is a device uint8[B]
+ * read where a POSTERIZE step applies to image k (values outside 1..8 are
+ * taken as the nearest of 1 and 8), or NULL for params->bits, which is
+ * ffcv_tone_batch itself.  Everything else, errors included, as there. */
+int ffcv_tone_batch_bits(void *stream, uint8_t *images, int batch, int height,
+                         int width, const ffcv_tone_params *params,
+                         const uint8_t *apply, void *workspace,
+                         uint64_t workspace_bytes, const uint8_t *bits);
+/* The same on host memory; with a POSTERIZE step, a bits[k] outside 1..8 is
+ * FFCV_EINVAL before any image is touched. */
+int ffcv_tone_batch_bits_host(uint8_t *images, int batch, int height,
+                              int width, const ffcv_tone_params *params,
+                              const uint8_t *apply, const uint8_t *bits);
 /* The host twin's table builder: tables[j][v] of step `kind` (bits read by
  * POSTERIZE) for a channel whose 256-bin histogram is hists[j], j < n. */
 int ffcv_tone_tables_host(int kind, int bits, const uint32_t *hists,
                           uint8_t *tables, int n);
+
+
+/* ------------------------------------------ TrivialAugmentWide --------- */
+/* The draws of the TrivialAugmentWide policy: every sample
+ * runs exactly ONE of 14 operations at a random strength.  Seeding contract
+ * op id 20; three draws per sample, always all three:
+ *   op  = min(13, int(rand() * 14))
+ *   bin = min(nbins - 1, int(rand() * nbins))
+ *   neg = rand() < 0.5
+ * v = table[op * nbins + bin], negated where neg and 1 <= op <= 9.  The table
+ * (float64 [14][nbins], built by the caller; device memory for the device
+ * entry) holds per operation:
+ *    0 identity            -
+ *    1 / 2 shear x / y     degrees
+ *    3 / 4 translate x / y whole pixels
+ *    5 rotate              degrees
+ *    6 / 7 / 8 brightness / saturation ("color") / contrast: ratio = 1 + v
+ *    9 sharpness           factor = float32(1 + v)
+ *   10 posterize           bits (1..8)
+ *   11 solarize            threshold (0..256)
+ *   12 / 13 autocontrast / equalize   -
+ * One lane per sample fills the arguments of the pixel launches:
+ *   op           : uint8[B]
+ *   cj_apply     : uint8[4][B], cj_ratio : float64[4][B] -- rows 0 .. 2 the
+ *                  program BRIGHTNESS, SATURATION, CONTRAST of
+ *                  ffcv_color_jitter_batch, row 3 the program SOLARIZE (a
+ *                  program has at most three steps); ratio 1 and threshold
+ *                  256 where the step does not apply
+ *   tone_apply   : uint8[3][B], tone_bits : uint8[B] -- the program POSTERIZE,
+ *                  AUTOCONTRAST, EQUALIZE of ffcv_tone_batch_bits (bits 8
+ *                  where posterize does not apply)
+ *   aff_apply    : uint8[B], aff_coef : int64[B][6] -- ffcv_affine_batch; the
+ *                  coefficients of affine_matrix (scale 1, the one non-zero
+ *                  argument v) for height x width images, the identity's
+ *                  where the operation is not geometric
+ *   sharp_apply  : uint8[B], 1 where op == 9 and 2 elsewhere, sharp_factor :
+ *                  float32[B] -- ffcv_sharpness_batch
+ *   status       : int32[B] or NULL (device entry only)
+ * FFCV_EINVAL for a null pointer, batch < 0, nbins outside 2..256, or a
+ * height or width outside 1..32767. */
+int ffcv_policy_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                           uint64_t loader_seed, uint64_t epoch, int nbins,
+                           const double *table, int height, int width,
+                           uint8_t *op, uint8_t *cj_apply, double *cj_ratio,
+                           uint8_t *tone_apply, uint8_t *tone_bits,
+                           uint8_t *aff_apply, int64_t *aff_coef,
+                           uint8_t *sharp_apply, float *sharp_factor,
+                           int32_t *status);
+int ffcv_policy_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                uint64_t loader_seed, uint64_t epoch,
+                                int nbins, const double *table, int height,
+                                int width, uint8_t *op, uint8_t *cj_apply,
+                                double *cj_ratio, uint8_t *tone_apply,
+                                uint8_t *tone_bits, uint8_t *aff_apply,
+                                int64_t *aff_coef, uint8_t *sharp_apply,
+                                float *sharp_factor);
 
 #ifdef __cplusplus
 }
