@@ -22,7 +22,7 @@ SOURCES = ['ffcv_common.hip', 'ffcv_rrc.hip', 'ffcv_jpeg.hip', 'ffcv_host.hip', 
            'ffcv_simple_aug.hip', 'ffcv_sharpness.hip', 'ffcv_policy.hip']
 HEADERS = ['api_internal.h', 'device_common.h', 'diag_hooks.h', 'color_common.h', 'blur_common.h', 'hue_common.h',
            'affine_common.h', 'tone_common.h', 'poison_common.h', 'jpeg_defs.h', 'jpeg_entropy.h', 'jpeg_idct.h',
-           'jpeg_color_resize.h', 'lds_stage.h', 'resize_out.h', 'sharpness_common.h']
+           'jpeg_color_resize.h', 'lds_stage.h', 'resize_out.h', 'sharpness_common.h', 'band_tiles.h']
 ARCH = os.environ.get('PYTORCH_ROCM_ARCH', 'gfx950').split(';')[0]
 
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-shared', '-std=c++17',

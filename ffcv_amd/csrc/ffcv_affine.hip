@@ -29,6 +29,10 @@
 //     staged once as one byte range.
 //   tiles: AFFINE_TILE_ROWS x AFFINE_TILE_COLS outputs; the staged footprint
 //     takes at most AFFINE_TILE_LDS bytes.
+//
+// The entries' argument check, the launch and the host twin's claim loop are
+// those of every out-of-place operator (api_internal.h: out_of_place_ok,
+// launch_tiles, host_images).
 #include <cmath>
 #include <cstring>
 
@@ -301,33 +305,16 @@ bool affine_draw_args_ok(const char *who, const void *ids, int batch, double p, 
 bool affine_args_ok(const char *who, const uint8_t *src, const uint8_t *dst, int batch, int height, int width,
                     int mode, const uint8_t *fill, const void *apply, const void *coef, uint64_t dst_stride,
                     uint64_t *stride) {
-  if (!src || !dst || !fill || !apply || !coef || batch < 0 || height < 1 || width < 1) {
-    ffcv::set_error("%s: invalid arguments", who);
+  if (!ffcv::out_of_place_ok(who, fill && apply && coef, src, dst, batch, height, width, FFCV_AFFINE_MAX_DIM,
+                             dst_stride, stride))
     return false;
-  }
-  if (height > FFCV_AFFINE_MAX_DIM || width > FFCV_AFFINE_MAX_DIM || (uint64_t)height * width * 3u > 0x7fffffffull) {
-    ffcv::set_error("%s: images of %dx%d exceed the supported %d per side and 2^31 - 1 bytes", who, height, width,
-                    FFCV_AFFINE_MAX_DIM);
+  if ((uint64_t)height * width * 3u > 0x7fffffffull) {
+    ffcv::set_error("%s: images of %dx%d exceed the supported 2^31 - 1 bytes", who, height, width);
     return false;
   }
   if (mode != FFCV_AFFINE_BILINEAR && mode != FFCV_AFFINE_NEAREST) {
     ffcv::set_error("%s: mode %d is neither FFCV_AFFINE_BILINEAR nor FFCV_AFFINE_NEAREST", who, mode);
     return false;
-  }
-  const uint64_t img = (uint64_t)height * width * 3;
-  *stride = dst_stride ? dst_stride : img;
-  if (*stride < img) {
-    ffcv::set_error("%s: dst_stride %llu for images of %llu bytes", who, (unsigned long long)dst_stride,
-                    (unsigned long long)img);
-    return false;
-  }
-  if (batch > 0) {
-    const uintptr_t a0 = (uintptr_t)src, a1 = a0 + (uint64_t)batch * img;
-    const uintptr_t b0 = (uintptr_t)dst, b1 = b0 + (uint64_t)(batch - 1) * *stride + img;
-    if (a0 < b1 && b0 < a1) {
-      ffcv::set_error("%s: src and dst overlap (the warp is out of place)", who);
-      return false;
-    }
   }
   return true;
 }
@@ -405,15 +392,9 @@ int ffcv_affine_batch(void *stream, const uint8_t *src, uint8_t *dst, int batch,
     return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
   const AffinePlan P = affine_plan(height, width);
-  const uint64_t blocks = (uint64_t)batch * P.nty * P.ntx;
-  if (blocks > 0x7fffffffull) {
-    ffcv::set_error("ffcv_affine_batch: %llu workgroups exceed one launch", (unsigned long long)blocks);
-    return FFCV_EINVAL;
-  }
-  hipLaunchKernelGGL(affine_warp_kernel, dim3((unsigned)blocks), dim3(AFFINE_THREADS), (size_t)P.lds,
-                     ffcv::as_stream(stream), src, dst, stride, height, width, mode, pack_fill(fill), apply, coef, P);
-  FFCV_LAUNCH_CHECK("affine_warp_kernel");
-  return FFCV_OK;
+  return ffcv::launch_tiles("ffcv_affine_batch", "affine_warp_kernel", affine_warp_kernel, stream,
+                            (uint64_t)batch * P.nty * P.ntx, AFFINE_THREADS, P.lds, src, dst, stride, height, width,
+                            mode, pack_fill(fill), apply, coef, P);
 }
 
 int ffcv_affine_batch_host(const uint8_t *src, uint8_t *dst, int batch, int height, int width, int mode,
@@ -424,18 +405,12 @@ int ffcv_affine_batch_host(const uint8_t *src, uint8_t *dst, int batch, int heig
                       dst_stride_bytes, &stride))
     return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
-  const uint64_t img = (uint64_t)height * width * 3;
   const uint32_t f = pack_fill(fill);
-  ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
-    for (uint64_t k = next.fetch_add(1); k < (uint64_t)batch; k = next.fetch_add(1)) {
-      const uint8_t *in = src + k * img;
-      uint8_t *out = dst + k * stride;
-      if (apply[k])
-        affine_image_host(in, out, height, width, mode, f, coef + k * 6);
-      else
-        std::memcpy(out, in, img);
-    }
-  });
+  ffcv::host_images(nthreads, batch, src, dst, (uint64_t)height * width * 3, stride,
+                    [&](uint64_t k, const uint8_t *in, uint8_t *out, int &) {
+                      if (apply[k]) affine_image_host(in, out, height, width, mode, f, coef + k * 6);
+                      return apply[k] != 0;
+                    });
   return FFCV_OK;
 }
 

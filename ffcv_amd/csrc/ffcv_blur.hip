@@ -18,23 +18,20 @@
 //      chunks cut by a row's (or the tile's) ends are stored byte by byte.
 //
 // The float32 intermediate never touches global memory.  An image whose
-// apply flag is 0 runs steps 1 and 4 only (a copy), on equal pieces of a
-// band's byte range instead of tiles.
+// apply flag is 0 runs steps 1 and 4 only (a copy).  The tiles, and a copy's
+// pieces, are the band tiles of band_tiles.h, with this kernel's constants:
 //
-//   whole image: 15 H W <= BLUR_LDS_BYTES -- one tile per image.  At the
-//     bound a workgroup takes 32.2 KiB of LDS, so four of them (16 waves, four
-//     per SIMD) share a CU's 160 KiB; a 32 x 32 image takes 15.2 KiB and the
-//     CU holds the eight workgroups (32 waves) that are its wave limit.
-//   bands: tiles of BLUR_BAND_ROWS rows; a band whose staged rows and float
-//     plane exceed BLUR_TILE_LDS at the image's width is split into column
-//     strips of the widest width that fits (blur_strip_cols).  A tile takes
-//     at most 40 KiB: four workgroups per CU again.
+//   whole image: 15 H W <= BLUR_LDS_BYTES.  At the bound a workgroup takes
+//     32.2 KiB of LDS, so four of them (16 waves, four per SIMD) share a CU's
+//     160 KiB; a 32 x 32 image takes 15.2 KiB and the CU holds the eight
+//     workgroups (32 waves) that are its wave limit.
+//   bands: BLUR_BAND_ROWS rows, in strips where the staged rows and the float
+//     plane exceed BLUR_TILE_LDS (40 KiB: four workgroups per CU again).
 #include <cmath>
-#include <cstring>
 
 #include "api_internal.h"
+#include "band_tiles.h"
 #include "blur_common.h"
-#include "lds_stage.h"
 
 #define BLUR_THREADS 256
 #define BLUR_LDS_BYTES 32768  // whole-image regime: 15 H W at most this
@@ -55,59 +52,22 @@ __global__ void __launch_bounds__(64) blur_draw_kernel(const uint64_t *__restric
   if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
 }
 
-// How a launch cuts an image into tiles, and the LDS a workgroup takes.
-struct BlurPlan {
-  int band_rows, strip_cols, nbands, nstrips;
-  uint32_t u8_bytes;  // the uint8 region (staged source, later the output bytes), a multiple of 16
-  uint32_t lds;       // dynamic LDS: weights | uint8 region | float plane
-};
-
-// LDS of a tile of `rows` x `cols` outputs at radius r in an H x W image
-static void blur_tile_lds(int H, int W, int rows, int cols, int r, uint32_t *u8_bytes, uint32_t *lds) {
-  const uint32_t nrows = (uint32_t)std::min(H, rows + 2 * r), cw = (uint32_t)std::min(W, cols + 2 * r);
-  // one range when every tile spans the width, else a range per row (a tile
-  // at the image's edge may still span it and stage one range: never more
-  // chunks than its rows take apart, from two rows on; one row is the same
-  // either way).  A copy stages one range of at most rows x cols pixels:
-  // never more than this.
-  const uint32_t one = lds_chunks(nrows * 3u * cw) * 16u, apart = nrows * lds_chunks(3u * cw) * 16u;
-  const uint32_t staged = cols >= W ? one : std::max(one, apart);
-  *u8_bytes = staged + 32u;  // + the pixel reads' and the output chunks' look-ahead
-  *lds = BLUR_W_LDS + *u8_bytes + nrows * (uint32_t)cols * 12u;
-}
-
-static BlurPlan blur_plan(int H, int W, int ksize) {
-  const int r = (ksize - 1) / 2;
-  BlurPlan P;
-  if ((uint64_t)H * W * 15u <= BLUR_LDS_BYTES) {
-    P.band_rows = H;
-    P.strip_cols = W;
-  } else {
-    P.band_rows = std::min(H, BLUR_BAND_ROWS);
-    uint32_t u8, lds;
-    blur_tile_lds(H, W, P.band_rows, W, r, &u8, &lds);
-    P.strip_cols = W;
-    if (lds > BLUR_TILE_LDS) {
-      // per strip column: 15 bytes per staged row; fixed: the halo columns, a row's chunk slack, the weights
-      const int nrows = std::min(H, P.band_rows + 2 * r);
-      int c = (BLUR_TILE_LDS - 176 - nrows * (6 * r + 32)) / (15 * nrows);
-      for (c = std::max(1, std::min(c, W));; c--) {
-        blur_tile_lds(H, W, P.band_rows, c, r, &u8, &lds);
-        if (lds <= BLUR_TILE_LDS || c == 1) break;
-      }
-      P.strip_cols = c;
-    }
-  }
-  P.nbands = (H + P.band_rows - 1) / P.band_rows;
-  P.nstrips = (W + P.strip_cols - 1) / P.strip_cols;
-  blur_tile_lds(H, W, P.band_rows, P.strip_cols, r, &P.u8_bytes, &P.lds);
-  return P;
+// The plan of a launch (band_tiles.h); dynamic LDS: weights | uint8 region
+// (staged source, later the output bytes) | float plane
+static BandPlan blur_plan(int H, int W, int ksize) {
+  const int r = (ksize - 1) / 2, nr = std::min(H, std::min(H, BLUR_BAND_ROWS) + 2 * r);  // a band's staged rows
+  // the first guess, per strip column: 15 bytes per staged row; fixed: the halo columns, a row's chunk slack, the
+  // weights
+  return band_plan(
+      H, W, (uint64_t)H * W * 15u <= BLUR_LDS_BYTES, BLUR_BAND_ROWS, BLUR_TILE_LDS, r,
+      [](uint32_t nrows, uint32_t, uint32_t cols) { return BLUR_W_LDS + nrows * cols * 12u; },
+      (BLUR_TILE_LDS - 176 - nr * (6 * r + 32)) / (15 * nr));
 }
 
 __global__ void __launch_bounds__(BLUR_THREADS)
     gaussian_blur_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint64_t dst_stride, int H, int W,
                          int ksize, const uint8_t *__restrict__ apply, const float *__restrict__ weights,
-                         BlurPlan P) {
+                         BandPlan P) {
   extern __shared__ uint4 blur_smem[];
   typedef uint32_t bx4_t __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(1))) bx4_t gx4_t;
@@ -115,6 +75,8 @@ __global__ void __launch_bounds__(BLUR_THREADS)
   bx4_t *s_u8 = (bx4_t *)((uint8_t *)blur_smem + BLUR_W_LDS);
   float *s_h = (float *)((uint8_t *)blur_smem + BLUR_W_LDS + P.u8_bytes);
   const int t = threadIdx.x;
+  // the workgroup's tile: BandTile (band_tiles.h) written out, like the staging and the write back below (on the
+  // struct the 32 x 32 launches measured slower, profiles/band_tiles_ab.txt)
   const uint32_t per = (uint32_t)P.nbands * P.nstrips;
   const uint32_t k = blockIdx.x / per, rem = blockIdx.x - k * per;
   const int band = rem / P.nstrips, strip = rem - band * P.nstrips;
@@ -288,33 +250,12 @@ bool blur_draw_args_ok(const char *who, const void *ids, int batch, double p, do
 // the checks of both pixel entries; *stride: the resolved dst stride
 bool blur_args_ok(const char *who, const uint8_t *src, const uint8_t *dst, int batch, int height, int width,
                   int ksize, const void *apply, const void *weights, uint64_t dst_stride, uint64_t *stride) {
-  if (!src || !dst || !apply || !weights || batch < 0 || height <= 0 || width <= 0) {
-    ffcv::set_error("%s: invalid arguments", who);
+  if (!ffcv::out_of_place_ok(who, apply && weights, src, dst, batch, height, width, BLUR_MAX_DIM, dst_stride, stride))
     return false;
-  }
-  if (height > BLUR_MAX_DIM || width > BLUR_MAX_DIM) {
-    ffcv::set_error("%s: images of %dx%d exceed the supported %d", who, height, width, BLUR_MAX_DIM);
-    return false;
-  }
   if (ksize < 1 || ksize > FFCV_BLUR_MAX_K || !(ksize & 1) || (ksize - 1) / 2 >= std::min(height, width)) {
     ffcv::set_error("%s: ksize %d on %dx%d images (odd, 1 .. %d, (ksize - 1) / 2 < min(height, width))", who, ksize,
                     height, width, FFCV_BLUR_MAX_K);
     return false;
-  }
-  const uint64_t img = (uint64_t)height * width * 3;
-  *stride = dst_stride ? dst_stride : img;
-  if (*stride < img) {
-    ffcv::set_error("%s: dst_stride %llu for images of %llu bytes", who, (unsigned long long)dst_stride,
-                    (unsigned long long)img);
-    return false;
-  }
-  if (batch > 0) {
-    const uintptr_t a0 = (uintptr_t)src, a1 = a0 + (uint64_t)batch * img;
-    const uintptr_t b0 = (uintptr_t)dst, b1 = b0 + (uint64_t)(batch - 1) * *stride + img;
-    if (a0 < b1 && b0 < a1) {
-      ffcv::set_error("%s: src and dst overlap (the blur is out of place)", who);
-      return false;
-    }
   }
   return true;
 }
@@ -385,16 +326,10 @@ int ffcv_gaussian_blur_batch(void *stream, const uint8_t *src, uint8_t *dst, int
                     dst_stride_bytes, &stride))
     return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
-  const BlurPlan P = blur_plan(height, width, ksize);
-  const uint64_t blocks = (uint64_t)batch * P.nbands * P.nstrips;
-  if (blocks > 0x7fffffffull) {
-    ffcv::set_error("ffcv_gaussian_blur_batch: %llu workgroups exceed one launch", (unsigned long long)blocks);
-    return FFCV_EINVAL;
-  }
-  hipLaunchKernelGGL(gaussian_blur_kernel, dim3((unsigned)blocks), dim3(BLUR_THREADS), (size_t)P.lds,
-                     ffcv::as_stream(stream), src, dst, stride, height, width, ksize, apply, weights, P);
-  FFCV_LAUNCH_CHECK("gaussian_blur_kernel");
-  return FFCV_OK;
+  const BandPlan P = blur_plan(height, width, ksize);
+  return ffcv::launch_tiles("ffcv_gaussian_blur_batch", "gaussian_blur_kernel", gaussian_blur_kernel, stream,
+                            (uint64_t)batch * P.nbands * P.nstrips, BLUR_THREADS, P.lds, src, dst, stride, height,
+                            width, ksize, apply, weights, P);
 }
 
 int ffcv_gaussian_blur_batch_host(const uint8_t *src, uint8_t *dst, int batch, int height, int width, int ksize,
@@ -405,18 +340,12 @@ int ffcv_gaussian_blur_batch_host(const uint8_t *src, uint8_t *dst, int batch, i
                     dst_stride_bytes, &stride))
     return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
-  const uint64_t img = (uint64_t)height * width * 3;
-  ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
-    std::vector<float> plane;
-    for (uint64_t k = next.fetch_add(1); k < (uint64_t)batch; k = next.fetch_add(1)) {
-      const uint8_t *in = src + k * img;
-      uint8_t *out = dst + k * stride;
-      if (apply[k])
-        blur_image_host(in, out, height, width, ksize, weights + k * FFCV_BLUR_WROW, plane);
-      else
-        std::memcpy(out, in, img);
-    }
-  });
+  ffcv::host_images<std::vector<float>>(
+      nthreads, batch, src, dst, (uint64_t)height * width * 3, stride,
+      [&](uint64_t k, const uint8_t *in, uint8_t *out, std::vector<float> &plane) {
+        if (apply[k]) blur_image_host(in, out, height, width, ksize, weights + k * FFCV_BLUR_WROW, plane);
+        return apply[k] != 0;
+      });
   return FFCV_OK;
 }
 

@@ -20,21 +20,20 @@
 //      chunks cut by a row's (or the tile's) ends are stored byte by byte.
 //
 // An image whose apply code is 2 is left alone: its workgroups exit at once.
-// One whose code is neither 1 nor 2 runs steps 1 and 3 only (a copy), on equal
-// pieces of a band's byte range instead of tiles.
+// One whose code is neither 1 nor 2 runs steps 1 and 3 only (a copy).  The
+// tiles, and a copy's pieces, are the band tiles of band_tiles.h at halo 1,
+// with this kernel's constants:
 //
-//   whole image: 6 H W <= SHARP_LDS_BYTES -- one tile per image (64 x 64).
-//   bands: tiles of SHARP_BAND_ROWS rows; a band whose staged rows and output
-//     bytes exceed SHARP_TILE_LDS at the image's width is split into column
-//     strips of the widest width that fits.
+//   whole image: 6 H W <= SHARP_LDS_BYTES (64 x 64).
+//   bands: SHARP_BAND_ROWS rows, in strips where the staged rows and the
+//     output bytes exceed SHARP_TILE_LDS.
 // A workgroup takes at most SHARP_TILE_LDS = 25 KiB, so six of them (24 waves)
 // share a CU's 160 KiB; a 32 x 32 image takes 6.1 KiB and the CU holds the
 // eight workgroups (32 waves) that are its wave limit.
 #include <cmath>
-#include <cstring>
 
 #include "api_internal.h"
-#include "lds_stage.h"
+#include "band_tiles.h"
 #include "sharpness_common.h"
 
 #define SHARP_THREADS 256
@@ -55,52 +54,17 @@ __global__ void __launch_bounds__(64) sharpness_draw_kernel(const uint64_t *__re
   if (status) status[k] = err ? FFCV_SAMPLE_RNG : FFCV_SAMPLE_OK;
 }
 
-// How a launch cuts an image into tiles, and the LDS a workgroup takes.
-struct SharpPlan {
-  int band_rows, strip_cols, nbands, nstrips;
-  uint32_t u8_bytes;  // the staged source with its look-ahead, a multiple of 16
-  uint32_t lds;       // dynamic LDS: lead | staged source | output bytes
-};
-
-// LDS of a tile of `rows` x `cols` outputs in an H x W image
-static void sharp_tile_lds(int H, int W, int rows, int cols, uint32_t *u8_bytes, uint32_t *lds) {
-  const uint32_t nrows = (uint32_t)std::min(H, rows + 2), cw = (uint32_t)std::min(W, cols + 2);
-  // one range when every tile spans the width, else a range per row (a tile
-  // at the image's edge may still span it and stage one range).  A copy
-  // stages one range of at most rows x cols pixels: never more than this.
-  const uint32_t one = lds_chunks(nrows * 3u * cw) * 16u, apart = nrows * lds_chunks(3u * cw) * 16u;
-  const uint32_t staged = cols >= W ? one : std::max(one, apart);
-  *u8_bytes = staged + 32u;  // + the dword reads' look-ahead
-  // the output bytes, dense, + the look-ahead of the chunks assembled from them
-  *lds = SHARP_LDS_LEAD + *u8_bytes + (((uint32_t)rows * 3u * cols + 15u) & ~15u) + 32u;
-}
-
-static SharpPlan sharp_plan(int H, int W) {
-  SharpPlan P;
-  if ((uint64_t)H * W * 6u <= SHARP_LDS_BYTES) {
-    P.band_rows = H;
-    P.strip_cols = W;
-  } else {
-    P.band_rows = std::min(H, SHARP_BAND_ROWS);
-    uint32_t u8, lds;
-    sharp_tile_lds(H, W, P.band_rows, W, &u8, &lds);
-    P.strip_cols = W;
-    if (lds > SHARP_TILE_LDS) {
-      // per strip column: 3 bytes per staged row and per output row; fixed: the halo columns, a row's chunk
-      // slack, the lead and the look-aheads
-      const int nrows = std::min(H, P.band_rows + 2);
-      int c = (SHARP_TILE_LDS - 96 - nrows * 38) / (3 * (nrows + P.band_rows));
-      for (c = std::max(1, std::min(c, W));; c--) {
-        sharp_tile_lds(H, W, P.band_rows, c, &u8, &lds);
-        if (lds <= SHARP_TILE_LDS || c == 1) break;
-      }
-      P.strip_cols = c;
-    }
-  }
-  P.nbands = (H + P.band_rows - 1) / P.band_rows;
-  P.nstrips = (W + P.strip_cols - 1) / P.strip_cols;
-  sharp_tile_lds(H, W, P.band_rows, P.strip_cols, &P.u8_bytes, &P.lds);
-  return P;
+// The plan of a launch (band_tiles.h); dynamic LDS: lead | uint8 region (the
+// staged source) | the output bytes, dense, + the look-ahead of the chunks
+// assembled from them
+static BandPlan sharp_plan(int H, int W) {
+  const int band = std::min(H, SHARP_BAND_ROWS), nr = std::min(H, band + 2);  // a band's rows, and its staged rows
+  // the first guess, per strip column: 3 bytes per staged row and per output row; fixed: the halo columns, a row's
+  // chunk slack, the lead and the look-aheads
+  return band_plan(
+      H, W, (uint64_t)H * W * 6u <= SHARP_LDS_BYTES, SHARP_BAND_ROWS, SHARP_TILE_LDS, 1,
+      [](uint32_t, uint32_t rows, uint32_t cols) { return SHARP_LDS_LEAD + ((rows * 3u * cols + 15u) & ~15u) + 32u; },
+      (SHARP_TILE_LDS - 96 - nr * 38) / (3 * (nr + band)));
 }
 
 // the ten bytes from LDS address p on (any alignment) as three dwords: four aligned reads joined by v_alignbyte
@@ -122,46 +86,31 @@ struct SharpTen {
 
 __global__ void __launch_bounds__(SHARP_THREADS)
     sharpness_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint64_t dst_stride, int H, int W,
-                     const uint8_t *__restrict__ apply, const float *__restrict__ factor, SharpPlan P) {
+                     const uint8_t *__restrict__ apply, const float *__restrict__ factor, BandPlan P) {
   extern __shared__ uint4 sharp_smem[];
   lds_x4_t *s_u8 = (lds_x4_t *)((uint8_t *)sharp_smem + SHARP_LDS_LEAD);
   uint8_t *s_out = (uint8_t *)s_u8 + P.u8_bytes;
   const int t = threadIdx.x;
-  const uint32_t per = (uint32_t)P.nbands * P.nstrips;
-  const uint32_t k = blockIdx.x / per, rem = blockIdx.x - k * per;
-  const int band = rem / P.nstrips, strip = rem - band * P.nstrips;
 
-  // the image's code (the same for the whole workgroup)
+  // the image's code (the same for the whole workgroup), and the tile
+  const uint32_t k = band_image(blockIdx.x, P);
   const uint32_t code = apply[k];
   if (code == 2) return;
   const bool on = code == 1;
   const float a = on ? factor[k] : 0.f;
-  const int y0 = band * P.band_rows, y1 = min(H, y0 + P.band_rows);
-  const int x0 = strip * P.strip_cols, x1 = min(W, x0 + P.strip_cols);
-  const int lo = max(0, y0 - 1), hi = min(H, y1 + 1), cl = max(0, x0 - 1), ch = min(W, x1 + 1);
-  const int nrows = hi - lo, cw = ch - cl, rows = y1 - y0, tc = x1 - x0;
+  const BandTile T(blockIdx.x, P, H, W, 1);
+  if (!on && T.cp_len == 0) return;
+  const int y0 = T.y0, x0 = T.x0, lo = T.lo, cl = T.cl, nrows = T.nrows, rows = T.rows, tc = T.tc;
 
-  // ---- stage source rows [lo, hi) x columns [cl, ch): one contiguous byte
-  // range when the rows span the width, else a range per row in whole chunks.
-  // A copy needs no halo and no columns: the band's rows are one byte range
-  // of the image, and the band's workgroups (one per strip) take an equal
-  // piece of it each, never more than a tile's bytes.
-  const uint64_t step = (uint64_t)W * 3u;
-  const uint32_t band_bytes = (uint32_t)rows * 3u * W, piece = (band_bytes + P.nstrips - 1) / P.nstrips;
-  const uint32_t cp0 = min(band_bytes, (uint32_t)strip * piece), cp_len = min(piece, band_bytes - cp0);
-  if (!on && cp_len == 0) return;
-  const uint64_t src0 = (uint64_t)(uintptr_t)src + (uint64_t)k * H * step +
-                        (on ? ((uint64_t)lo * W + cl) * 3u : (uint64_t)y0 * step + cp0);
-  const bool span = !on || cw == W;
-  const int n_srows = span ? 1 : nrows;
-  const uint32_t srow_bytes = !on ? cp_len : (span ? (uint32_t)nrows * 3u * W : 3u * cw);
-  const int nchr = (int)lds_chunks(srow_bytes);
-  stage_rows<SHARP_THREADS>(t, src0, step, n_srows, srow_bytes, nchr, s_u8);
+  // ---- stage the tile's source, or the copy's piece
+  const BandRows S = T.source(!on, H, W, src);
+  const int nchr = (int)lds_chunks(S.bytes);
+  stage_rows<SHARP_THREADS>(t, S.a0, T.step, S.n, S.bytes, nchr, s_u8);
   __syncthreads();
 
   const int rowb = 3 * tc;  // output bytes per tile row
   if (on) {
-    const LdsRows<> R = lds_rows(s_u8, src0, step, span, nchr);
+    const LdsRows<> R = lds_rows(s_u8, S.a0, T.step, S.span, nchr);
     const int ng = (rowb + 3) >> 2;
     const int left = 3 * (x0 - cl) - 3;  // from a staged row's first byte to the left tap of the tile's byte 0
     const int gb0 = 3 * x0, gb_last = 3 * W - 3;
@@ -206,13 +155,9 @@ __global__ void __launch_bounds__(SHARP_THREADS)
 
   // ---- write back: the tile's bytes, dense, or the copy's piece as staged.
   // Rows that span the width leave as one byte range.
-  const bool ospan = !on || tc == W;
-  const uint32_t orow_bytes = !on ? cp_len : (ospan ? band_bytes : 3u * tc);
-  const uint64_t dst0 = (uint64_t)(uintptr_t)dst + (uint64_t)k * dst_stride +
-                        (on ? ((uint64_t)y0 * W + x0) * 3u : (uint64_t)y0 * step + cp0);
-  const uint8_t *s_from = on ? s_out : (const uint8_t *)s_u8 + (int)(src0 & 15);
-  write_back_rows<SHARP_THREADS>(t, dst0, step, ospan ? 1 : rows, orow_bytes,
-                                 [&](int y) { return s_from + y * rowb; });
+  const BandRows D = T.dest(!on, W, dst, dst_stride);
+  const uint8_t *s_from = on ? s_out : (const uint8_t *)s_u8 + (int)(S.a0 & 15);
+  write_back_rows<SHARP_THREADS>(t, D.a0, T.step, D.n, D.bytes, [&](int y) { return s_from + y * rowb; });
 }
 
 namespace {
@@ -222,35 +167,6 @@ bool sharp_draw_args_ok(const char *who, const void *ids, int batch, double p, d
   if (batch < 0 || !ids || !apply || !factor_out || !(p >= 0.0 && p <= 1.0) || !(factor >= 0.0 && factor <= 16.0)) {
     ffcv::set_error("%s: invalid arguments (p %g, factor %g)", who, p, factor);
     return false;
-  }
-  return true;
-}
-
-// the checks of both pixel entries; *stride: the resolved dst stride
-bool sharp_args_ok(const char *who, const uint8_t *src, const uint8_t *dst, int batch, int height, int width,
-                   const void *apply, const void *factor, uint64_t dst_stride, uint64_t *stride) {
-  if (!src || !dst || !apply || !factor || batch < 0 || height <= 0 || width <= 0) {
-    ffcv::set_error("%s: invalid arguments", who);
-    return false;
-  }
-  if (height > SHARP_MAX_DIM || width > SHARP_MAX_DIM) {
-    ffcv::set_error("%s: images of %dx%d exceed the supported %d", who, height, width, SHARP_MAX_DIM);
-    return false;
-  }
-  const uint64_t img = (uint64_t)height * width * 3;
-  *stride = dst_stride ? dst_stride : img;
-  if (*stride < img) {
-    ffcv::set_error("%s: dst_stride %llu for images of %llu bytes", who, (unsigned long long)dst_stride,
-                    (unsigned long long)img);
-    return false;
-  }
-  if (batch > 0) {
-    const uintptr_t a0 = (uintptr_t)src, a1 = a0 + (uint64_t)batch * img;
-    const uintptr_t b0 = (uintptr_t)dst, b1 = b0 + (uint64_t)(batch - 1) * *stride + img;
-    if (a0 < b1 && b0 < a1) {
-      ffcv::set_error("%s: src and dst overlap (the operation is out of place)", who);
-      return false;
-    }
   }
   return true;
 }
@@ -311,40 +227,28 @@ uint64_t ffcv_sharpness_strip_cols(int height, int width) {
 int ffcv_sharpness_batch(void *stream, const uint8_t *src, uint8_t *dst, int batch, int height, int width,
                          const uint8_t *apply, const float *factor, uint64_t dst_stride_bytes) {
   uint64_t stride;
-  if (!sharp_args_ok("ffcv_sharpness_batch", src, dst, batch, height, width, apply, factor, dst_stride_bytes,
-                     &stride))
+  if (!ffcv::out_of_place_ok("ffcv_sharpness_batch", apply && factor, src, dst, batch, height, width, SHARP_MAX_DIM,
+                             dst_stride_bytes, &stride))
     return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
-  const SharpPlan P = sharp_plan(height, width);
-  const uint64_t blocks = (uint64_t)batch * P.nbands * P.nstrips;
-  if (blocks > 0x7fffffffull) {
-    ffcv::set_error("ffcv_sharpness_batch: %llu workgroups exceed one launch", (unsigned long long)blocks);
-    return FFCV_EINVAL;
-  }
-  hipLaunchKernelGGL(sharpness_kernel, dim3((unsigned)blocks), dim3(SHARP_THREADS), (size_t)P.lds,
-                     ffcv::as_stream(stream), src, dst, stride, height, width, apply, factor, P);
-  FFCV_LAUNCH_CHECK("sharpness_kernel");
-  return FFCV_OK;
+  const BandPlan P = sharp_plan(height, width);
+  return ffcv::launch_tiles("ffcv_sharpness_batch", "sharpness_kernel", sharpness_kernel, stream,
+                            (uint64_t)batch * P.nbands * P.nstrips, SHARP_THREADS, P.lds, src, dst, stride, height,
+                            width, apply, factor, P);
 }
 
 int ffcv_sharpness_batch_host(const uint8_t *src, uint8_t *dst, int batch, int height, int width,
                               const uint8_t *apply, const float *factor, uint64_t dst_stride_bytes, int nthreads) {
   uint64_t stride;
-  if (!sharp_args_ok("ffcv_sharpness_batch_host", src, dst, batch, height, width, apply, factor, dst_stride_bytes,
-                     &stride))
+  if (!ffcv::out_of_place_ok("ffcv_sharpness_batch_host", apply && factor, src, dst, batch, height, width,
+                             SHARP_MAX_DIM, dst_stride_bytes, &stride))
     return FFCV_EINVAL;
   if (batch == 0) return FFCV_OK;
-  const uint64_t img = (uint64_t)height * width * 3;
-  ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
-    for (uint64_t k = next.fetch_add(1); k < (uint64_t)batch; k = next.fetch_add(1)) {
-      const uint8_t *in = src + k * img;
-      uint8_t *out = dst + k * stride;
-      if (apply[k] == 1)
-        sharp_image_host(in, out, height, width, factor[k]);
-      else if (apply[k] != 2)
-        std::memcpy(out, in, img);
-    }
-  });
+  ffcv::host_images(nthreads, batch, src, dst, (uint64_t)height * width * 3, stride,
+                    [&](uint64_t k, const uint8_t *in, uint8_t *out, int &) {
+                      if (apply[k] == 1) sharp_image_host(in, out, height, width, factor[k]);
+                      return apply[k] == 1 || apply[k] == 2;  // 2: dst is left alone
+                    });
   return FFCV_OK;
 }
 

@@ -607,6 +607,25 @@ def _u8_batch_dims(images, who):
     return int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
 
 
+def _u8_out_of_place_dims(src, dst, who):
+    """_u8_batch_dims of the ``src`` of an out-of-place ``*_host`` entry, whose
+    ``dst`` is such an array too, of the same image shape, with room for B."""
+    dims = _u8_batch_dims(src, who)
+    if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous and
+            dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
+        raise TypeError(f'{who}: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are required')
+    return dims
+
+
+def _per_image(who, name, a, dtype, *shape):
+    """``a`` as a C-contiguous per-image array of ``dtype`` and ``shape`` (B, ...); (B,): of B values."""
+    a = np.ascontiguousarray(a, dtype)
+    a = a.reshape(-1) if len(shape) == 1 else a
+    if a.shape != shape:
+        raise TypeError(f'{who}: {name} {shape} is required, got {a.shape}')
+    return a
+
+
 def translate_draw_batch(ids, loader_seed, epoch, padding, yx, status=None, stream=None):
     """RandomTranslate windows (y, x) of the batch on the device (op id 4)."""
     _check(lib().ffcv_translate_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]),
@@ -852,9 +871,7 @@ def gaussian_blur_batch(src, dst, ksize, apply, weights, dst_stride=0, stream=No
     """Blur (apply[k] != 0) or copy each image of a dense device uint8
     (B, H, W, 3) batch into ``dst`` (ffcv_gaussian_blur_batch): one launch, out
     of place; apply device uint8 (B,), weights device float32 (B, 32)."""
-    if src.dim() != 4 or int(src.shape[3]) != 3 or src.element_size() != 1 or not src.is_contiguous():
-        raise TypeError('gaussian_blur_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
-    B, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    B, H, W = _u8_batch_dims(src, 'gaussian_blur_batch')
     _check(lib().ffcv_gaussian_blur_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(ksize), _p(apply),
                                           _p(weights), int(dst_stride)), 'ffcv_gaussian_blur_batch')
     return dst
@@ -862,17 +879,9 @@ def gaussian_blur_batch(src, dst, ksize, apply, weights, dst_stride=0, stream=No
 
 def gaussian_blur_batch_host(src: np.ndarray, dst: np.ndarray, ksize, apply, weights, nthreads=1):
     """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
-    if not (isinstance(src, np.ndarray) and isinstance(dst, np.ndarray) and src.dtype == np.uint8 and
-            dst.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3 and src.flags.c_contiguous and
-            dst.flags.c_contiguous and dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
-        raise TypeError('gaussian_blur_batch_host: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are '
-                        'required')
-    B, H, W = (int(x) for x in src.shape[:3])
-    apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
-    weights = np.ascontiguousarray(weights, np.float32)
-    if apply.size != B or weights.shape != (B, BLUR_WROW):
-        raise TypeError(f'gaussian_blur_batch_host: apply ({B},) and weights ({B}, {BLUR_WROW}) are required, got '
-                        f'{apply.shape} and {weights.shape}')
+    B, H, W = _u8_out_of_place_dims(src, dst, 'gaussian_blur_batch_host')
+    apply = _per_image('gaussian_blur_batch_host', 'apply', apply, np.uint8, B)
+    weights = _per_image('gaussian_blur_batch_host', 'weights', weights, np.float32, B, BLUR_WROW)
     _check(lib().ffcv_gaussian_blur_batch_host(_p(src), _p(dst), B, H, W, int(ksize), _p(apply), _p(weights), 0,
                                                int(max(1, nthreads))), 'ffcv_gaussian_blur_batch_host')
     return dst[:B]
@@ -917,9 +926,7 @@ def sharpness_batch(src, dst, apply, factor, dst_stride=0, stream=None):
     0), sharpen with factor[k] (1) or leave ``dst`` alone (2)
     (ffcv_sharpness_batch): one launch, out of place; apply device uint8 (B,),
     factor device float32 (B,)."""
-    if src.dim() != 4 or int(src.shape[3]) != 3 or src.element_size() != 1 or not src.is_contiguous():
-        raise TypeError('sharpness_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
-    B, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    B, H, W = _u8_batch_dims(src, 'sharpness_batch')
     _check(lib().ffcv_sharpness_batch(_stream(stream), _p(src), _p(dst), B, H, W, _p(apply), _p(factor),
                                       int(dst_stride)), 'ffcv_sharpness_batch')
     return dst
@@ -927,17 +934,9 @@ def sharpness_batch(src, dst, apply, factor, dst_stride=0, stream=None):
 
 def sharpness_batch_host(src: np.ndarray, dst: np.ndarray, apply, factor, nthreads=1):
     """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
-    if not (isinstance(src, np.ndarray) and isinstance(dst, np.ndarray) and src.dtype == np.uint8 and
-            dst.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3 and src.flags.c_contiguous and
-            dst.flags.c_contiguous and dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
-        raise TypeError('sharpness_batch_host: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are '
-                        'required')
-    B, H, W = (int(x) for x in src.shape[:3])
-    apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
-    factor = np.ascontiguousarray(factor, np.float32).reshape(-1)
-    if apply.size != B or factor.size != B:
-        raise TypeError(f'sharpness_batch_host: apply ({B},) and factor ({B},) are required, got '
-                        f'{apply.shape} and {factor.shape}')
+    B, H, W = _u8_out_of_place_dims(src, dst, 'sharpness_batch_host')
+    apply = _per_image('sharpness_batch_host', 'apply', apply, np.uint8, B)
+    factor = _per_image('sharpness_batch_host', 'factor', factor, np.float32, B)
     _check(lib().ffcv_sharpness_batch_host(_p(src), _p(dst), B, H, W, _p(apply), _p(factor), 0,
                                            int(max(1, nthreads))), 'ffcv_sharpness_batch_host')
     return dst[:B]
@@ -1218,9 +1217,7 @@ def affine_batch(src, dst, mode, fill, apply, coef, dst_stride=0, stream=None):
     """Warp (apply[k] != 0) or copy each image of a dense device uint8
     (B, H, W, 3) batch into ``dst`` (ffcv_affine_batch): one launch, out of
     place; apply device uint8 (B,), coef device int64 (B, 6)."""
-    if src.dim() != 4 or int(src.shape[3]) != 3 or src.element_size() != 1 or not src.is_contiguous():
-        raise TypeError('affine_batch: a contiguous uint8 (B, H, W, 3) tensor is required')
-    B, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    B, H, W = _u8_batch_dims(src, 'affine_batch')
     f = fill_u8(fill)
     _check(lib().ffcv_affine_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef),
                                    int(dst_stride)), 'ffcv_affine_batch')
@@ -1229,17 +1226,10 @@ def affine_batch(src, dst, mode, fill, apply, coef, dst_stride=0, stream=None):
 
 def affine_batch_host(src: np.ndarray, dst: np.ndarray, mode, fill, apply, coef, nthreads=1):
     """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
-    if not (isinstance(src, np.ndarray) and isinstance(dst, np.ndarray) and src.dtype == np.uint8 and
-            dst.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3 and src.flags.c_contiguous and
-            dst.flags.c_contiguous and dst.shape[1:] == src.shape[1:] and dst.shape[0] >= src.shape[0]):
-        raise TypeError('affine_batch_host: C-contiguous uint8 (B, H, W, 3) arrays of one image shape are required')
-    B, H, W = (int(x) for x in src.shape[:3])
+    B, H, W = _u8_out_of_place_dims(src, dst, 'affine_batch_host')
     f = fill_u8(fill)
-    apply = np.ascontiguousarray(apply, np.uint8).reshape(-1)
-    coef = np.ascontiguousarray(coef, np.int64)
-    if apply.size != B or coef.shape != (B, 6):
-        raise TypeError(f'affine_batch_host: apply ({B},) and coef ({B}, 6) are required, got {apply.shape} and '
-                        f'{coef.shape}')
+    apply = _per_image('affine_batch_host', 'apply', apply, np.uint8, B)
+    coef = _per_image('affine_batch_host', 'coef', coef, np.int64, B, 6)
     _check(lib().ffcv_affine_batch_host(_p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef), 0,
                                         int(max(1, nthreads))), 'ffcv_affine_batch_host')
     return dst[:B]

@@ -26,7 +26,6 @@ import torch as ch
 from ..libffcv import fill_u8
 from ..pipeline.allocation_query import AllocationQuery
 from ..pipeline.state import State
-from ..pipeline import runtime
 from .u8_image import _U8ImageOp
 
 _MODES = {'bilinear': 0, 'nearest': 1}       # FFCV_AFFINE_*
@@ -130,37 +129,22 @@ class RandomAffine(_U8ImageOp):
 
     def generate_code(self) -> Callable:
         from .. import libffcv as L
-        name, p, mode, fill = self._name, self.p, _MODES[self.interpolation], self.fill_u8()
+        p, mode, fill = self.p, _MODES[self.interpolation], self.fill_u8()
         key = ('affine', id(self))
 
-        def affine(images, dst, indices):
-            ctx = runtime.current()
+        def device(ctx, images, out):
             H, W = int(images.shape[1]), int(images.shape[2])
-            rg = self.ranges(H, W)
-            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
-                if not images.is_contiguous():
-                    raise TypeError(f'{name}: a contiguous (B, H, W, 3) batch is required')
-                B = int(images.shape[0])
-                apply = ctx.device_buffer(key + ('apply',), ctx.batch_size, ch.uint8)
-                coef = ctx.device_buffer(key + ('coef',), ctx.batch_size * 6, ch.int64)
-                L.affine_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, p, rg, H, W, apply, coef, None,
-                                    ctx.stream)
-                out = dst[:B]
-                L.affine_batch(images, out, mode, fill, apply, coef, 0, ctx.stream)
-                return out
-            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
-            src = images.numpy() if isinstance(images, ch.Tensor) else images
-            src = np.ascontiguousarray(src)
-            B = len(indices)
-            out = dst[:B]
-            out_np = out.numpy() if isinstance(out, ch.Tensor) else out
-            from ..pipeline.compiler import Compiler
-            apply, coef = L.affine_draw_batch_host(np.asarray(indices, np.uint64), seed, epoch, p, rg, H, W)
-            L.affine_batch_host(src[:B], out_np, mode, fill, apply, coef, nthreads=max(1, int(Compiler.num_threads)))
-            return out
-        affine.is_parallel = True
-        affine.with_indices = True
-        return affine
+            apply = ctx.device_buffer(key + ('apply',), ctx.batch_size, ch.uint8)
+            coef = ctx.device_buffer(key + ('coef',), ctx.batch_size * 6, ch.int64)
+            L.affine_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, p, self.ranges(H, W), H, W, apply, coef,
+                                None, ctx.stream)
+            L.affine_batch(images, out, mode, fill, apply, coef, 0, ctx.stream)
+
+        def host(seed, epoch, ids, src, out_np, nthreads):
+            H, W = src.shape[1:3]
+            apply, coef = L.affine_draw_batch_host(ids, seed, epoch, p, self.ranges(H, W), H, W)
+            L.affine_batch_host(src, out_np, mode, fill, apply, coef, nthreads=nthreads)
+        return self.out_of_place_code(device, host)
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         _, shape = self.check_u8_images(previous_state)

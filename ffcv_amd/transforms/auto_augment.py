@@ -42,7 +42,6 @@ import torch as ch
 from ..libffcv import fill_u8
 from ..pipeline.allocation_query import AllocationQuery
 from ..pipeline.state import State
-from ..pipeline import runtime
 from .affine import _MODES
 from .u8_image import _U8ImageOp
 
@@ -118,51 +117,36 @@ class TrivialAugmentWide(_U8ImageOp):
         nbins, mode, fill, table = self.num_magnitude_bins, _MODES[self.interpolation], fill_u8(self.fill), self.table
         key = ('trivial_augment', id(self))
 
-        def trivial_augment(images, dst, indices):
-            ctx = runtime.current()
-            H, W = int(images.shape[1]), int(images.shape[2])
-            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
-                if not images.is_contiguous():
-                    raise TypeError('TrivialAugmentWide: a contiguous (B, H, W, 3) batch is required')
-                B = int(images.shape[0])
-                d = {}
-                for name, dt, shape in L.POLICY_ARRAYS:
-                    shp = shape(B)
-                    n = int(np.prod(shp))
-                    d[name] = ctx.device_buffer(key + (name,), int(np.prod(shape(ctx.batch_size))),
-                                                getattr(ch, np.dtype(dt).name))[:n].view(shp)
-                L.policy_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, nbins, self.device_table(images.device),
-                                    H, W, d, None, ctx.stream)
-                cj_ws = tone_ws = None
-                if H * W * 3 > L.color_jitter_lds_bytes():
-                    cj_ws = ctx.device_buffer(key + ('cj_ws',), ctx.batch_size, ch.int64)[:B]
-                if H * W * 3 > L.tone_lds_bytes():
-                    tone_ws = ctx.device_buffer(key + ('tone_ws',), 768 * ctx.batch_size, ch.int32)[:768 * B]
-                L.color_jitter_batch(images, _CJ_STEPS, d['cj_apply'][:3], d['cj_ratio'][:3], cj_ws, ctx.stream)
-                L.color_jitter_batch(images, _SOLARIZE_STEPS, d['cj_apply'][3:], d['cj_ratio'][3:], None, ctx.stream)
-                L.tone_batch_bits(images, _TONE_STEPS, d['tone_apply'], d['tone_bits'], tone_ws, ctx.stream)
-                out = dst[:B]
-                L.affine_batch(images, out, mode, fill, d['aff_apply'], d['aff_coef'], 0, ctx.stream)
-                L.sharpness_batch(images, out, d['sharp_apply'], d['sharp_factor'], 0, ctx.stream)
-                return out
-            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
-            src = images.numpy() if isinstance(images, ch.Tensor) else images
-            B = len(indices)
-            src = np.ascontiguousarray(src[:B])
-            out = dst[:B]
-            out_np = out.numpy() if isinstance(out, ch.Tensor) else out
-            from ..pipeline.compiler import Compiler
-            nthreads = max(1, int(Compiler.num_threads))
-            d = L.policy_draw_batch_host(np.asarray(indices, np.uint64), seed, epoch, nbins, table, H, W)
+        def device(ctx, images, out):
+            B, H, W = (int(x) for x in images.shape[:3])
+            d = {}
+            for name, dt, shape in L.POLICY_ARRAYS:
+                shp = shape(B)
+                n = int(np.prod(shp))
+                d[name] = ctx.device_buffer(key + (name,), int(np.prod(shape(ctx.batch_size))),
+                                            getattr(ch, np.dtype(dt).name))[:n].view(shp)
+            L.policy_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, nbins, self.device_table(images.device),
+                                H, W, d, None, ctx.stream)
+            cj_ws = tone_ws = None
+            if H * W * 3 > L.color_jitter_lds_bytes():
+                cj_ws = ctx.device_buffer(key + ('cj_ws',), ctx.batch_size, ch.int64)[:B]
+            if H * W * 3 > L.tone_lds_bytes():
+                tone_ws = ctx.device_buffer(key + ('tone_ws',), 768 * ctx.batch_size, ch.int32)[:768 * B]
+            L.color_jitter_batch(images, _CJ_STEPS, d['cj_apply'][:3], d['cj_ratio'][:3], cj_ws, ctx.stream)
+            L.color_jitter_batch(images, _SOLARIZE_STEPS, d['cj_apply'][3:], d['cj_ratio'][3:], None, ctx.stream)
+            L.tone_batch_bits(images, _TONE_STEPS, d['tone_apply'], d['tone_bits'], tone_ws, ctx.stream)
+            L.affine_batch(images, out, mode, fill, d['aff_apply'], d['aff_coef'], 0, ctx.stream)
+            L.sharpness_batch(images, out, d['sharp_apply'], d['sharp_factor'], 0, ctx.stream)
+
+        def host(seed, epoch, ids, src, out_np, nthreads):
+            H, W = src.shape[1:3]
+            d = L.policy_draw_batch_host(ids, seed, epoch, nbins, table, H, W)
             L.color_jitter_batch_host(src, _CJ_STEPS, d['cj_apply'][:3], d['cj_ratio'][:3])
             L.color_jitter_batch_host(src, _SOLARIZE_STEPS, d['cj_apply'][3:], d['cj_ratio'][3:])
             L.tone_batch_bits_host(src, _TONE_STEPS, d['tone_apply'], d['tone_bits'])
             L.affine_batch_host(src, out_np, mode, fill, d['aff_apply'], d['aff_coef'], nthreads=nthreads)
             L.sharpness_batch_host(src, out_np, d['sharp_apply'], d['sharp_factor'], nthreads=nthreads)
-            return out
-        trivial_augment.is_parallel = True
-        trivial_augment.with_indices = True
-        return trivial_augment
+        return self.out_of_place_code(device, host)
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         _, shape = self.check_u8_images(previous_state)

@@ -17,12 +17,10 @@ import math
 import numbers
 from typing import Callable, Optional, Tuple
 
-import numpy as np
 import torch as ch
 
 from ..pipeline.allocation_query import AllocationQuery
 from ..pipeline.state import State
-from ..pipeline import runtime
 from .u8_image import _U8ImageOp
 
 
@@ -61,34 +59,18 @@ class GaussianBlur(_U8ImageOp):
         ksize, (lo, hi), p = self.kernel_size, self.sigma, self.p
         key = ('gaussian_blur', id(self))
 
-        def gaussian_blur(images, dst, indices):
-            ctx = runtime.current()
-            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
-                if not images.is_contiguous():
-                    raise TypeError('GaussianBlur: a contiguous (B, H, W, 3) batch is required')
-                B = int(images.shape[0])
-                apply = ctx.device_buffer(key + ('apply',), ctx.batch_size, ch.uint8)
-                sigma = ctx.device_buffer(key + ('sigma',), ctx.batch_size, ch.float64)
-                weights = ctx.device_buffer(key + ('weights',), ctx.batch_size * L.BLUR_WROW, ch.float32)
-                L.blur_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, p, lo, hi, ksize, apply, sigma, weights,
-                                  None, ctx.stream)
-                out = dst[:B]
-                L.gaussian_blur_batch(images, out, ksize, apply, weights, 0, ctx.stream)
-                return out
-            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
-            src = images.numpy() if isinstance(images, ch.Tensor) else images
-            src = np.ascontiguousarray(src)
-            B = len(indices)
-            out = dst[:B]
-            out_np = out.numpy() if isinstance(out, ch.Tensor) else out
-            from ..pipeline.compiler import Compiler
-            apply, _, weights = L.blur_draw_batch_host(np.asarray(indices, np.uint64), seed, epoch, p, lo, hi, ksize)
-            L.gaussian_blur_batch_host(src[:B], out_np, ksize, apply, weights,
-                                       nthreads=max(1, int(Compiler.num_threads)))
-            return out
-        gaussian_blur.is_parallel = True
-        gaussian_blur.with_indices = True
-        return gaussian_blur
+        def device(ctx, images, out):
+            apply = ctx.device_buffer(key + ('apply',), ctx.batch_size, ch.uint8)
+            sigma = ctx.device_buffer(key + ('sigma',), ctx.batch_size, ch.float64)
+            weights = ctx.device_buffer(key + ('weights',), ctx.batch_size * L.BLUR_WROW, ch.float32)
+            L.blur_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, p, lo, hi, ksize, apply, sigma, weights,
+                              None, ctx.stream)
+            L.gaussian_blur_batch(images, out, ksize, apply, weights, 0, ctx.stream)
+
+        def host(seed, epoch, ids, src, out_np, nthreads):
+            apply, _, weights = L.blur_draw_batch_host(ids, seed, epoch, p, lo, hi, ksize)
+            L.gaussian_blur_batch_host(src, out_np, ksize, apply, weights, nthreads=nthreads)
+        return self.out_of_place_code(device, host)
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         _, shape = self.check_u8_images(previous_state)

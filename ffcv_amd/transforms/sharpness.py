@@ -17,12 +17,10 @@ import math
 import numbers
 from typing import Callable, Optional, Tuple
 
-import numpy as np
 import torch as ch
 
 from ..pipeline.allocation_query import AllocationQuery
 from ..pipeline.state import State
-from ..pipeline import runtime
 from .u8_image import _U8ImageOp
 
 
@@ -54,32 +52,17 @@ class RandomAdjustSharpness(_U8ImageOp):
         factor, p = self.sharpness_factor, self.p
         key = ('sharpness', id(self))
 
-        def adjust_sharpness(images, dst, indices):
-            ctx = runtime.current()
-            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
-                if not images.is_contiguous():
-                    raise TypeError('RandomAdjustSharpness: a contiguous (B, H, W, 3) batch is required')
-                B = int(images.shape[0])
-                apply = ctx.device_buffer(key + ('apply',), ctx.batch_size, ch.uint8)
-                factors = ctx.device_buffer(key + ('factor',), ctx.batch_size, ch.float32)
-                L.sharpness_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, p, factor, apply, factors, None,
-                                       ctx.stream)
-                out = dst[:B]
-                L.sharpness_batch(images, out, apply, factors, 0, ctx.stream)
-                return out
-            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
-            src = images.numpy() if isinstance(images, ch.Tensor) else images
-            src = np.ascontiguousarray(src)
-            B = len(indices)
-            out = dst[:B]
-            out_np = out.numpy() if isinstance(out, ch.Tensor) else out
-            from ..pipeline.compiler import Compiler
-            apply, factors = L.sharpness_draw_batch_host(np.asarray(indices, np.uint64), seed, epoch, p, factor)
-            L.sharpness_batch_host(src[:B], out_np, apply, factors, nthreads=max(1, int(Compiler.num_threads)))
-            return out
-        adjust_sharpness.is_parallel = True
-        adjust_sharpness.with_indices = True
-        return adjust_sharpness
+        def device(ctx, images, out):
+            apply = ctx.device_buffer(key + ('apply',), ctx.batch_size, ch.uint8)
+            factors = ctx.device_buffer(key + ('factor',), ctx.batch_size, ch.float32)
+            L.sharpness_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, p, factor, apply, factors, None,
+                                   ctx.stream)
+            L.sharpness_batch(images, out, apply, factors, 0, ctx.stream)
+
+        def host(seed, epoch, ids, src, out_np, nthreads):
+            apply, factors = L.sharpness_draw_batch_host(ids, seed, epoch, p, factor)
+            L.sharpness_batch_host(src, out_np, apply, factors, nthreads=nthreads)
+        return self.out_of_place_code(device, host)
 
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         self.check_u8_images(previous_state)

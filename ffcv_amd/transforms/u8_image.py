@@ -8,6 +8,7 @@ import numpy as np
 import torch as ch
 
 from ..pipeline.allocation_query import AllocationQuery
+from ..pipeline import runtime
 from ..pipeline.operation import Operation
 from ..pipeline.state import State
 
@@ -51,6 +52,34 @@ class _U8ImageOp(Operation):
         def fused(images, *_):
             return images
         return fused
+
+    def out_of_place_code(self, device, host):
+        """The code of an operation that writes a batch into ``dst``.  On a
+        device batch ``device(ctx, images, out)`` makes the draws and the pixel
+        launches; on a host one ``host(seed, epoch, ids, src, out_np, nthreads)``
+        makes the host draws and runs the host twins on C-contiguous arrays.
+        ``out``: the batch's part of ``dst``, which the code returns."""
+        label = self._label
+
+        def code(images, dst, indices):
+            ctx = runtime.current()
+            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
+                if not images.is_contiguous():
+                    raise TypeError(f'{label}: a contiguous (B, H, W, 3) batch is required')
+                out = dst[:int(images.shape[0])]
+                device(ctx, images, out)
+                return out
+            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
+            src = np.ascontiguousarray(images.numpy() if isinstance(images, ch.Tensor) else images)
+            B = len(indices)
+            out = dst[:B]
+            out_np = out.numpy() if isinstance(out, ch.Tensor) else out
+            from ..pipeline.compiler import Compiler
+            host(seed, epoch, np.asarray(indices, np.uint64), src[:B], out_np, max(1, int(Compiler.num_threads)))
+            return out
+        code.is_parallel = True
+        code.with_indices = True
+        return code
 
     def check_u8_images(self, previous_state: State):
         return check_u8_images(self._label, previous_state)
