@@ -44,6 +44,16 @@ static_assert(FB_AC <= 11, "FB_AC > 11 is not supported: a 12-bit build failed t
 #define K1_WCHUNK 4
 #endif
 static_assert(K1_WCHUNK >= 1 && K1_WCHUNK <= 8, "K1_WCHUNK outside 1..8 is not supported: past 8 a flat block idles through most of its chunk (tools/sync_sim.c chunks)");
+// K1 decode extent (entropy_passes): the entropy decode stops at the linear
+// estimate of where the crop window's last MCU row ends, plus a margin of
+// K1_EXT_REL / 256 of the stream and K1_EXT_ABS bits (chosen with the host
+// model, tools/k1_extent_model.py; K1_EXT_REL >= 256 always decodes in full).
+#ifndef K1_EXT_REL
+#define K1_EXT_REL 8
+#endif
+#ifndef K1_EXT_ABS
+#define K1_EXT_ABS 2048
+#endif
 #ifndef BAND
 #define BAND 16  // K2 output rows per workgroup
 #endif

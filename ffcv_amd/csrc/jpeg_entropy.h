@@ -893,14 +893,40 @@ FFCV_DEV bool entropy_passes(JShared &S, const TB &T, const JpegArgs &a, int k, 
     info->lane_off[1][t] = o1;
     info->lane_off[2][t] = o2;
   };
-  uint32_t nthr = (total_bits + 191) / 192;
-  nthr = max(1u, min(nthr, (uint32_t)JT));
-  const uint32_t cbits = (total_bits + nthr - 1) / nthr;
-  const bool active = t < (int)nthr;
-  const uint32_t my_end = active ? (t == (int)nthr - 1 ? total_bits : min(total_bits, (t + 1) * cbits)) : 0;
-  // ---------------------------------------------------- entropy index ----
+  // ---------------------------------------------------- decode extent ----
+  // A baseline stream is sequential: the blocks up to the end of the last MCU
+  // row that holds a window block are needed (block boundaries, DC sums), the
+  // rest of the scan is not.  need_blocks is that prefix in MCU order; the
+  // lane ranges are laid over [0, ext), the linear estimate of its end plus a
+  // margin (K1_EXT_*), instead of the whole stream.  The estimate is checked
+  // once the rounds have converged (P4), and a prefix that fell short is
+  // decoded again over the full extent.  A sample with an entropy index
+  // record is always decoded in full: a record holds the lane states of the
+  // full partition and later epochs skip the sync rounds with it.
   uint32_t *rec = nullptr;
   if (a.eidx && sample_id < a.eidx_n) rec = a.eidx + sample_id * (EIDX_LANES * EIDX_WORDS);
+  const uint32_t nblocks = wuni((uint32_t)S.nblocks);
+  int my_last = 0;  // last MCU row with a window block
+  for (int c = 0; c < S.ncomp; c++) my_last = max(my_last, dsmall(S.wy1[c], S.vs[c]));
+  const uint32_t need_rows = wuni((uint32_t)my_last + 1u);
+  const uint32_t need_blocks = min(nblocks, need_rows * wuni((uint32_t)(S.mcux * S.bpm)));
+  uint32_t ext = total_bits;
+  if (need_blocks < nblocks && !rec && K1_EXT_REL < 256) {
+    const uint32_t est = total_bits / wuni((uint32_t)S.mcuy) * need_rows;
+    ext = min(total_bits, est + (total_bits >> 8) * K1_EXT_REL + K1_EXT_ABS);
+  }
+  bool fell_back = false;
+  uint32_t nthr, cbits, my_end;
+  bool active;
+  auto lay_ranges = [&]() {  // up to JT lane ranges of >= 192 bits over [0, ext)
+    nthr = (ext + 191) / 192;
+    nthr = max(1u, min(nthr, (uint32_t)JT));
+    cbits = (ext + nthr - 1) / nthr;
+    active = t < (int)nthr;
+    my_end = active ? (t == (int)nthr - 1 ? ext : min(ext, (t + 1) * cbits)) : 0;
+  };
+  lay_ranges();
+  // ---------------------------------------------------- entropy index ----
   if (rec) {
     const uint32_t w0 = __builtin_nontemporal_load(rec + EIDX_WORDS * t);
     const uint32_t w1 = __builtin_nontemporal_load(rec + EIDX_WORDS * t + 1);
@@ -938,66 +964,82 @@ FFCV_DEV bool entropy_passes(JShared &S, const TB &T, const JpegArgs &a, int k, 
   }
   // ------------------------------------------------------------- P3 ----
   STAMP(3);
-  DecState g;
-  g.pos = active ? t * cbits : 0;
-  g.z = 0;
-  g.ph = 0;
-  uint32_t my_cnt = 0;
-  int my_nev = 0, my_cb = 0, my_eb = 0;  // events: count, buffer, block count of slot 0
-  DecState e = g;
+  DecState g, e;
+  uint32_t my_cnt, blk_base;
+  int my_nev, my_cb, my_eb;  // events: count, buffer, block count of slot 0
   uint32_t it_lane = 0, it_wave = 0;  // diagnostics: loop iterations (max over lanes per round)
-  // event stride: NEV events spread over a lane's expected block count
-  const uint32_t evq = ((uint32_t)S.nblocks / nthr + NEV) / NEV;
-  const int esh = evq <= 1 ? 0 : 32 - __clz((int)(evq - 1));
-  if (active) e = sync_range<false>(S, T, words, g, my_end, t, my_cnt, my_nev, my_cb, my_eb, g, esh, it_lane);
-  if (a.dbg) it_wave += __reduce_max_sync(~0ull, it_lane);
   int rounds = 0;
+  bool any_bad;
+  // (a loop: run once, and once more over the whole stream when [0, ext) held
+  // fewer than need_blocks blocks; the rounds write only LDS events and
+  // registers, the write pass starts after the coverage check)
   for (;;) {
-    DecState ng;
-    ng.pos = lane_prev0(e.pos, t);
-    ng.z = (int)lane_prev0((uint32_t)e.z, t);
-    ng.ph = (int)lane_prev0((uint32_t)e.ph, t);
-    const bool changed = active && t > 0 && (ng.pos != g.pos || ng.z != g.z || ng.ph != g.ph);
-    if (!__any(changed)) break;
-    rounds++;
-    if (changed) {
-      g = ng;
-      if (g.pos >= my_end) {
-        e = g;
-        my_cnt = 0;
-        my_nev = 0;
-        my_eb = 0;
-      } else {
-        it_lane = 0;
-        e = sync_range<true>(S, T, words, g, my_end, t, my_cnt, my_nev, my_cb, my_eb, e, esh, it_lane);
+    g.pos = active ? t * cbits : 0;
+    g.z = 0;
+    g.ph = 0;
+    my_cnt = 0;
+    my_nev = my_cb = my_eb = 0;
+    e = g;
+    // event stride: NEV events spread over a lane's expected block count
+    const uint32_t exp_blocks = ext == total_bits ? nblocks : min(nblocks, ext / max(1u, total_bits / nblocks));
+    const uint32_t evq = (exp_blocks / nthr + NEV) / NEV;
+    const int esh = evq <= 1 ? 0 : 32 - __clz((int)(evq - 1));
+    if (active) e = sync_range<false>(S, T, words, g, my_end, t, my_cnt, my_nev, my_cb, my_eb, g, esh, it_lane);
+    if (a.dbg) it_wave += __reduce_max_sync(~0ull, it_lane);
+    for (;;) {
+      DecState ng;
+      ng.pos = lane_prev0(e.pos, t);
+      ng.z = (int)lane_prev0((uint32_t)e.z, t);
+      ng.ph = (int)lane_prev0((uint32_t)e.ph, t);
+      const bool changed = active && t > 0 && (ng.pos != g.pos || ng.z != g.z || ng.ph != g.ph);
+      if (!__any(changed)) break;
+      rounds++;
+      if (changed) {
+        g = ng;
+        if (g.pos >= my_end) {
+          e = g;
+          my_cnt = 0;
+          my_nev = 0;
+          my_eb = 0;
+        } else {
+          it_lane = 0;
+          e = sync_range<true>(S, T, words, g, my_end, t, my_cnt, my_nev, my_cb, my_eb, e, esh, it_lane);
+        }
       }
+      if (a.dbg) it_wave += __reduce_max_sync(~0ull, changed ? it_lane : 0u);
     }
-    if (a.dbg) it_wave += __reduce_max_sync(~0ull, changed ? it_lane : 0u);
+    if (!active) my_cnt = 0;
+
+    // ----------------------------------------------------------- P4 ----
+    STAMP(4);
+    blk_base = wave_exscan(my_cnt);
+    bool bad_lane = false;
+    if (active) {
+      int64_t cur = g.z == 0 ? (int64_t)blk_base : (int64_t)blk_base - 1;
+      bad_lane = cur < 0 || (cur % S.bpm) != g.ph;  // inconsistent stream
+    }
+    // Blocks completed in [0, ext): those started, less the one the last lane
+    // range left unfinished (the pad bits of a whole stream may start one
+    // block more).  Fewer than need_blocks over a shortened extent: the
+    // estimate fell short, decode the whole stream.  Fewer over the whole
+    // stream (truncated data, an early marker) is a corrupt stream: libjpeg
+    // pads it with zero bits and leaves the remaining MCUs grey, this path
+    // reports it.
+    const uint32_t nstarted = lane_read(blk_base + my_cnt, JT - 1);
+    const uint32_t zlast = lane_read((uint32_t)e.z, (int)wuni(nthr - 1));
+    const bool is_short = nstarted - (zlast != 0 ? 1u : 0u) < need_blocks;
+    any_bad = __ballot(bad_lane) != 0 || is_short;
+    if (!is_short || ext == total_bits) break;
+    ext = total_bits;
+    fell_back = true;
+    lay_ranges();
   }
-  if (!active) my_cnt = 0;
   if (a.dbg && t == 0) {
     a.dbg[(uint64_t)k * 16 + 12] = (uint64_t)rounds;
-    a.dbg[(uint64_t)k * 16 + 13] = (uint64_t)nthr;
+    // nthr, whether the full-extent pass had to follow, the extent decoded
+    a.dbg[(uint64_t)k * 16 + 13] = (uint64_t)nthr | (fell_back ? 0x100ull : 0ull) | (uint64_t)ext << 32;
     a.dbg[(uint64_t)k * 16 + 14] = (uint64_t)it_wave;
   }
-
-  // ------------------------------------------------------------- P4 ----
-  STAMP(4);
-  const uint32_t blk_base = wave_exscan(my_cnt);
-  bool bad_lane = false;
-  if (active) {
-    int64_t cur = g.z == 0 ? (int64_t)blk_base : (int64_t)blk_base - 1;
-    bad_lane = cur < 0 || (cur % S.bpm) != g.ph;  // inconsistent stream
-  }
-  // A stream that ends before its last block does (truncated data, an early
-  // marker) is corrupt too: libjpeg pads it with zero bits and leaves the
-  // remaining MCUs grey, this path reports it.  Blocks started, less the one
-  // the last lane range left unfinished (the pad bits of a whole stream may
-  // start one block more).
-  const uint32_t nstarted = lane_read(blk_base + my_cnt, JT - 1);
-  const uint32_t zlast = lane_read((uint32_t)e.z, (int)wuni(nthr - 1));
-  const bool is_short = nstarted - (zlast != 0 ? 1u : 0u) < (uint32_t)S.nblocks;
-  const bool any_bad = __ballot(bad_lane) != 0 || is_short;
   if (rec && !any_bad) {  // publish this sample's converged lane states
     const int64_t cur = g.z == 0 ? (int64_t)blk_base : (int64_t)blk_base - 1;
     uint32_t w0 = active ? g.pos : 0u, w1 = active ? (uint32_t)g.z | ((uint32_t)g.ph << 8) : 0u,

@@ -3,7 +3,7 @@
 Runs one batch with the debug stamp buffer enabled (diagnostic only: the
 stamps are written to their own buffer and never read by the kernel).
 """
-import ctypes, os, sys, time
+import ctypes, os, re, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -51,7 +51,22 @@ for n, (i0, i1) in (('  header load', (0, 10)), ('  parse+barrier', (10, 1))):
 tot = (d[:, 9] - d[:, 0]) / 100.0
 print('  total        mean', tot.mean(), 'max', tot.max())
 print('span of K1 us', (d[:, 9].max() - d[:, 0].min()) / 100.0)
-print('rounds hist', np.bincount(d[:, 12].astype(int))[:20], 'nthr mean', d[:, 13].mean())
+print('rounds hist', np.bincount(d[:, 12].astype(int))[:20], 'nthr mean', (d[:, 13] & 0xff).mean())
+# decode extent (slot 13: lanes | fell back << 8 | extent << 32) against the de-stuffed stream's bits
+# (the scan up to EOI less its stuffed zero bytes, counted here on the host)
+def scan_bits(blob):
+    b = blob.tobytes()
+    sos = b.index(b'\xff\xda')
+    scan = b[sos + 2 + ((b[sos + 2] << 8) | b[sos + 3]):]
+    scan = scan[:re.search(rb'\xff[^\x00]', scan).start()]
+    return 8 * (len(scan) - scan.count(b'\xff\x00'))
+uniq = np.unique(idx)
+bits = np.zeros(len(offs)); bits[uniq] = [scan_bits(tile[offs[i]:offs[i] + sizes[i]]) for i in uniq]
+ext = (d[:, 13].view(np.uint64) >> np.uint64(32)).astype(np.float64)
+fr = ext / bits[idx]
+assert fr.max() <= 1.0
+print(f'decode extent: mean fraction of the stream {fr.mean():.4f}, images decoded in full {np.mean(fr == 1):.4f}, '
+      f'fell back {np.mean((d[:, 13] >> 8) & 1):.5f}')
 st = (d[:, 0] - d[:, 0].min()) / 100.0
 print('start offsets us: p50', np.median(st), 'max', st.max())
 print('sync wave-iterations mean', d[:, 14].mean(), 'max', d[:, 14].max(), '| write wave-iterations mean', d[:, 15].mean(), 'max', d[:, 15].max())

@@ -5,6 +5,9 @@
 // latency proxy: rounds end at a workgroup barrier) and the total work.
 // heur 12 (`sync_sim file.jpg 64 12`) models the write pass instead: chunks
 // per image for K1_WCHUNK = 1..8 (profiles/k1_wchunk_model.txt).
+// heur 13 (`sync_sim file.jpg 64 13`) prints where every MCU row ends against
+// the linear estimate K1's decode extent uses (tools/k1_extent_model.py,
+// profiles/k1_extent_model.txt).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -188,7 +191,7 @@ int main(int argc, char **argv) {
   if (getenv("SIM_NEV")) nev_max = atoi(getenv("SIM_NEV"));
   if (getenv("SIM_SPARSE")) sparse = atoi(getenv("SIM_SPARSE"));
   long p = 2;
-  int hs[3], vs[3], cid[3], nc = 0, scan = 0;
+  int hs[3], vs[3], cid[3], nc = 0, scan = 0, img_h = 0, img_w = 0;
   while (!scan) {
     while (d[p] == 0xFF) p++;
     int m = d[p++];
@@ -203,6 +206,8 @@ int main(int argc, char **argv) {
         o += 17 + tot;
       }
     } else if (m == 0xC0) {
+      img_h = (s[1] << 8) | s[2];
+      img_w = (s[3] << 8) | s[4];
       nc = s[5];
       for (int c = 0; c < nc; c++) {
         cid[c] = s[6 + 3 * c];
@@ -353,6 +358,43 @@ int main(int argc, char **argv) {
     printf("\nacsteps:");
     for (int q = 0; q <= 64; q++)
       if (hist[q]) printf(" %d:%ld", q, hist[q]);
+    printf("\n");
+    return 0;
+  }
+  if (heur == 13) {  // MCU-row ends: `sync_sim file.jpg 64 13`
+    // K1's decode extent (entropy_passes) stops at the linear estimate of
+    // where the crop window's last MCU row ends, plus a margin.  Prints, for
+    // every MCU row r, the true bit position where its last block ends and
+    // the kernel's estimate bits / mcuy * (r + 1); tools/k1_extent_model.py
+    // picks the margin from these (profiles/k1_extent_model.txt).
+    int hmax = 1, vmax = 1;
+    for (int c = 0; c < nc; c++) {
+      if (hs[c] > hmax) hmax = hs[c];
+      if (vs[c] > vmax) vmax = vs[c];
+    }
+    if (nc == 1) hmax = vmax = 1;
+    const int mcux = (img_w + 8 * hmax - 1) / (8 * hmax), mcuy = (img_h + 8 * vmax - 1) / (8 * vmax);
+    const long per_row = (long)mcux * bpm;
+    printf("rows: bits %u mcux %d mcuy %d bpm %d |", tbits, mcux, mcuy, bpm);
+    uint32_t pos = 0;
+    int z = 0, ph = 0, row = 0;
+    long nblk = 0;
+    while (pos < tbits && row < mcuy) {
+      int len, bad, ti = z == 0 ? ph_dc[ph] : ph_ac[ph];
+      int v = sym(ti, pos, &len, &bad);
+      int sz = z == 0 ? v : (v & 15), r = z == 0 ? 0 : v >> 4;
+      pos += len + sz;
+      int zac = sz ? z + r + 1 : (r == 15 ? z + 16 : 64);
+      z = z == 0 ? 1 : zac;
+      if (z >= 64) {
+        z = 0;
+        ph = (ph + 1) % bpm;
+        if (++nblk == per_row * (row + 1)) {
+          printf(" %d:%u:%u", row, pos, tbits / mcuy * (row + 1));
+          row++;
+        }
+      }
+    }
     printf("\n");
     return 0;
   }
