@@ -246,6 +246,10 @@ _SIGS = {
                                        c_float, c_float, c_int]),
     'ffcv_replace_label_batch': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                          c_int64]),
+    'ffcv_cutmix_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int64,
+                                  c_void_p, c_int]),
+    'ffcv_cutmix_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int64,
+                                       c_void_p, c_int, c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1319,6 +1323,93 @@ def mixup_onehot_batch(labels3, out, status, stream=None):
                         'int32 (n,) status are required')
     _check(lib().ffcv_mixup_onehot_batch(_stream(stream), _p(labels3), _p(out), n, int(out.shape[1]), _p(status)),
            'ffcv_mixup_onehot_batch')
+    return out
+
+
+CUTMIX_LAYOUTS = ('auto', 'hwc', 'chw')
+
+
+def cutmix_geometry(who, x, layout='auto'):
+    """(planes, height, width, pixel_bytes) of a batch of images, a torch
+    tensor or a numpy array with the samples along axis 0, as
+    ffcv_cutmix_batch takes it.  ``'auto'``: a 4-D tensor with
+    channels-last strides that is not contiguous is the NCHW view of NHWC
+    storage (``H, W = shape[2:]``, one plane); anything contiguous is
+    ``(B, H, W, C...)``.  ``'hwc'`` requires the second reading, ``'chw'`` a
+    contiguous ``(B, C, H, W)`` (C planes)."""
+    if layout not in CUTMIX_LAYOUTS:
+        raise ValueError(f'{who}: layout must be one of {CUTMIX_LAYOUTS}, got {layout!r}')
+    is_np = isinstance(x, np.ndarray)
+    itemsize = int(x.itemsize if is_np else x.element_size())
+    ndim = x.ndim if is_np else x.dim()
+    shape = tuple(int(v) for v in x.shape)
+    if ndim < 3 or min(shape) < 1:
+        raise TypeError(f'{who}: a non-empty batch of images (B, H, W, ...) is required, got shape {shape}')
+    contiguous = bool(x.flags.c_contiguous) if is_np else x.is_contiguous()
+    if layout == 'auto' and not is_np and ndim == 4 and not contiguous:
+        import torch
+        if x.is_contiguous(memory_format=torch.channels_last):
+            return 1, shape[2], shape[3], shape[1] * itemsize
+    if not contiguous:
+        raise TypeError(f'{who}: the images must be contiguous, or with layout=\'auto\' the NCHW view of channels-last '
+                        f'storage, got shape {shape} and strides '
+                        f'{tuple(x.strides) if is_np else tuple(x.stride())}')
+    if layout == 'chw':
+        if ndim != 4:
+            raise TypeError(f'{who}: layout=\'chw\' takes (B, C, H, W), got shape {shape}')
+        return shape[1], shape[2], shape[3], itemsize
+    pixel = itemsize
+    for v in shape[3:]:
+        pixel *= v
+    return 1, shape[1], shape[2], pixel
+
+
+def _cutmix_boxes_ok(n_boxes, n, batch_size, same_box):
+    nb = -(-n // int(batch_size)) if int(batch_size) > 0 else 0
+    return n_boxes >= 4 * (nb if same_box else n)
+
+
+def cutmix_batch(inp, out, boxes, batch_size, same_box, layout='auto', stream=None):
+    """ImageCutMix on a device batch of any dtype of 1, 2, 4 or 8 bytes
+    (ffcv_cutmix_batch): ``out[i] = inp[i]`` with the box ``[y1:y2, x1:x2]``
+    taken from the neighbour, which is sample i - 1, or the last sample of i's
+    own batch of ``batch_size`` when i is its first.  ``boxes``: device
+    int32 rows of ``(y1, x1, y2, x2)``, one per sample or, with ``same_box``,
+    one per batch; they are clamped to the image on the device.  ``inp`` and
+    ``out`` are dense, laid out alike, with the samples outermost in memory,
+    and must not overlap; ``layout`` as in :func:`cutmix_geometry`."""
+    import torch
+    if out.dtype != inp.dtype:
+        raise TypeError(f'cutmix_batch: tensors of one dtype are required, got {inp.dtype} and {out.dtype}')
+    n = int(inp.shape[0]) if inp.dim() else 0
+    if inp.dim() < 1 or n < 1 or inp.numel() < 1 or not _dense_like(inp, out) or \
+            int(inp.stride(0)) * n != inp.numel():
+        raise TypeError('cutmix_batch: inp and out must be dense tensors of the same shape and strides with the '
+                        f'samples outermost in memory, got shapes {tuple(inp.shape)}, {tuple(out.shape)} and '
+                        f'strides {tuple(inp.stride())}, {tuple(out.stride())}')
+    planes, h, w, pb = cutmix_geometry('cutmix_batch', inp, layout)
+    if boxes.dtype != torch.int32 or not boxes.is_contiguous() or \
+            not _cutmix_boxes_ok(boxes.numel(), n, batch_size, same_box):
+        raise TypeError('cutmix_batch: boxes must be a contiguous int32 tensor with one (y1, x1, y2, x2) per '
+                        + ('batch' if same_box else 'sample'))
+    _check(lib().ffcv_cutmix_batch(_stream(stream), _p(inp), _p(out), n, planes, h, w, pb, int(batch_size), _p(boxes),
+                                   int(bool(same_box))), 'ffcv_cutmix_batch')
+    return out
+
+
+def cutmix_batch_host(inp: np.ndarray, out: np.ndarray, boxes, batch_size, same_box, layout='auto', nthreads=1):
+    """The same on C-contiguous numpy arrays of any dtype (samples along
+    axis 0), with memcpy of row segments."""
+    if out.dtype != inp.dtype or inp.shape != out.shape or inp.ndim < 1 or inp.size < 1 or \
+            not inp.flags.c_contiguous or not out.flags.c_contiguous:
+        raise TypeError('cutmix_batch_host: C-contiguous arrays of one dtype and shape are required')
+    planes, h, w, pb = cutmix_geometry('cutmix_batch_host', inp, layout)
+    n = int(inp.shape[0])
+    boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1)
+    if not _cutmix_boxes_ok(boxes.size, n, batch_size, same_box):
+        raise TypeError('cutmix_batch_host: boxes needs one (y1, x1, y2, x2) per ' + ('batch' if same_box else 'sample'))
+    _check(lib().ffcv_cutmix_batch_host(_p(inp), _p(out), n, planes, h, w, pb, int(batch_size), _p(boxes),
+                                        int(bool(same_box)), int(max(1, nthreads))), 'ffcv_cutmix_batch_host')
     return out
 
 

@@ -11,6 +11,7 @@ from .hue import RandomHue, RandomColorJitter
 from .affine import RandomAffine, RandomRotation
 from .tone import RandomPosterize, RandomAutocontrast, RandomEqualize, RandomInvert
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
+from .cutmix import ImageCutMix, LabelCutMix, ImageMixupCutMix, LabelMixupCutMix
 from .poison import Poison
 from .replace_label import ReplaceLabel
 from .ops import ToTensor, ToDevice, ToTorchImage, Convert, View
@@ -25,4 +26,5 @@ __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 
            'RandomColorJitter',
            'RandomAffine', 'RandomRotation', 'TrivialAugmentWide',
            'RandomPosterize', 'RandomAutocontrast', 'RandomEqualize', 'RandomInvert',
-           'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'Poison', 'ReplaceLabel']
+           'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'ImageCutMix', 'LabelCutMix', 'ImageMixupCutMix',
+           'LabelMixupCutMix', 'Poison', 'ReplaceLabel']

@@ -956,6 +956,34 @@ int ffcv_mixup_batch_host(const void *in, void *out, int64_t n_samples,
 int ffcv_mixup_onehot_batch(void *stream, const float *labels3, float *out,
                             int64_t n, int64_t num_classes, int32_t *status);
 
+/* -------------------------------------------------------- cutmix ------ */
+/* ImageCutMix.  A sample is planes x height rows of width * pixel_bytes
+ * bytes, dense, the samples outermost: NHWC of any dtype is planes = 1,
+ * pixel_bytes = C * itemsize; contiguous NCHW is planes = C, pixel_bytes =
+ * itemsize.  Batches and neighbours are those of ffcv_mixup_batch.  With the
+ * box (y1, x1, y2, x2) = boxes[4 * s ..] when same_box, else boxes[4 * i ..],
+ * each bound clamped to the image here:
+ *   out[i] = in[i];  out[i][p][y1:y2][x1:x2] = in[nb][p][y1:y2][x1:x2]
+ * for every plane p; a box with y1 >= y2 or x1 >= x2 is empty.  The bytes are
+ * moved, never interpreted, so any dtype is served.  A launch of several
+ * batches is one call.
+ *   in, out : device, at any byte alignment; the two ranges must not overlap
+ *   boxes   : device int32, aligned to 4 bytes, one box per sample, or one
+ *             per batch when same_box
+ * FFCV_EINVAL, before any launch, for a null pointer, a count <= 0,
+ * pixel_bytes outside 1..64, a sample of more than 2^31 - 1 bytes or a batch
+ * of more than 2^62, or overlapping ranges. */
+int ffcv_cutmix_batch(void *stream, const void *in, void *out,
+                      int64_t n_samples, int32_t planes, int32_t height,
+                      int32_t width, int32_t pixel_bytes, int64_t batch_size,
+                      const int32_t *boxes, int same_box);
+/* The same on host memory (boxes on the host too) with memcpy of row
+ * segments, over nthreads threads (one sample at a time each). */
+int ffcv_cutmix_batch_host(const void *in, void *out, int64_t n_samples,
+                           int32_t planes, int32_t height, int32_t width,
+                           int32_t pixel_bytes, int64_t batch_size,
+                           const int32_t *boxes, int same_box, int nthreads);
+
 /* -------------------------------------------- poison, replace label ---- */
 /* poisoning.py: Poison.  Every sample i of a dense uint8
  * [n_samples][sample_elems] array whose dataset index sample_ids[i] is in
