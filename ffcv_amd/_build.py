@@ -19,10 +19,12 @@ OUT = os.path.join(HERE, 'libffcv_hip.so')
 SOURCES = ['ffcv_common.hip', 'ffcv_rrc.hip', 'ffcv_jpeg.hip', 'ffcv_host.hip', 'ffcv_cpu_jpeg.hip',
            'ffcv_color.hip', 'ffcv_mixup.hip', 'ffcv_poison.hip', 'ffcv_gather.hip', 'ffcv_rrc_images.hip',
            'ffcv_blur.hip', 'ffcv_hue.hip', 'ffcv_affine.hip', 'ffcv_tone.hip', 'ffcv_standalone.hip',
-           'ffcv_simple_aug.hip', 'ffcv_sharpness.hip', 'ffcv_policy.hip', 'ffcv_cutmix.hip']
+           'ffcv_simple_aug.hip', 'ffcv_sharpness.hip', 'ffcv_policy.hip', 'ffcv_cutmix.hip',
+           'ffcv_erase.hip']
 HEADERS = ['api_internal.h', 'device_common.h', 'diag_hooks.h', 'color_common.h', 'blur_common.h', 'hue_common.h',
            'affine_common.h', 'tone_common.h', 'poison_common.h', 'jpeg_defs.h', 'jpeg_entropy.h', 'jpeg_idct.h',
-           'jpeg_color_resize.h', 'lds_stage.h', 'resize_out.h', 'sharpness_common.h', 'band_tiles.h']
+           'jpeg_color_resize.h', 'lds_stage.h', 'resize_out.h', 'sharpness_common.h', 'band_tiles.h',
+           'erase_common.h']
 ARCH = os.environ.get('PYTORCH_ROCM_ARCH', 'gfx950').split(';')[0]
 
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-shared', '-std=c++17',

@@ -250,6 +250,14 @@ _SIGS = {
                                   c_void_p, c_int]),
     'ffcv_cutmix_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int64,
                                        c_void_p, c_int, c_int]),
+    'ffcv_erase_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p, c_void_p,
+                                      c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'ffcv_erase_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_void_p, c_void_p, c_int,
+                                           c_int, c_void_p, c_void_p]),
+    'ffcv_erase_batch': (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int,
+                                 c_int32, c_void_p, c_void_p]),
+    'ffcv_erase_batch_host': (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int, c_int32,
+                                      c_void_p, c_void_p, c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1411,6 +1419,122 @@ def cutmix_batch_host(inp: np.ndarray, out: np.ndarray, boxes, batch_size, same_
     _check(lib().ffcv_cutmix_batch_host(_p(inp), _p(out), n, planes, h, w, pb, int(batch_size), _p(boxes),
                                         int(bool(same_box)), int(max(1, nthreads))), 'ffcv_cutmix_batch_host')
     return out
+
+
+ERASE_CONSTANT, ERASE_NOISE = 0, 1  # FFCV_ERASE_*
+ERASE_TABLE = 4096                  # entries of the noise table
+
+
+def _pair(who, name, v):
+    r = np.ascontiguousarray([float(x) for x in v], dtype=np.float64)
+    if r.shape != (2,):
+        raise TypeError(f'{who}: {name} must be two numbers')
+    return r
+
+
+def erase_draw_batch(ids, loader_seed, epoch, p, scale, ratio, height, width, boxes, keys=None, status=None,
+                     stream=None):
+    """RandomErasing's draws of the batch on the device (op id 21): boxes
+    device int32 (B, 4) of ``(y, x, h, w)``, ``h = w = 0`` where nothing is
+    erased; keys device 8-byte integers (B,), the noise keys (op id 22), or
+    None."""
+    B = int(ids.shape[0])
+    if boxes.element_size() != 4 or boxes.numel() < 4 * B or not boxes.is_contiguous() or \
+            (keys is not None and (keys.element_size() != 8 or keys.numel() < B or not keys.is_contiguous())):
+        raise TypeError('erase_draw_batch: boxes must be a contiguous int32 (B, 4) tensor and keys a contiguous '
+                        '8-byte integer (B,) tensor')
+    s, r = _pair('erase_draw_batch', 'scale', scale), _pair('erase_draw_batch', 'ratio', ratio)
+    _check(lib().ffcv_erase_draw_batch(_stream(stream), _p(ids), B, _seed64(loader_seed), int(epoch), float(p), _p(s),
+                                       _p(r), int(height), int(width), _p(boxes), _p(keys), _p(status)),
+           'ffcv_erase_draw_batch')
+
+
+def erase_draw_batch_host(ids, loader_seed, epoch, p, scale, ratio, height, width):
+    """The same draws on the host: (boxes int32 (B, 4), keys uint64 (B,))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+    s, r = _pair('erase_draw_batch_host', 'scale', scale), _pair('erase_draw_batch_host', 'ratio', ratio)
+    boxes = np.zeros((ids.size, 4), np.int32)
+    keys = np.zeros(ids.size, np.uint64)
+    _check(lib().ffcv_erase_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch), float(p), _p(s),
+                                            _p(r), int(height), int(width), _p(boxes), _p(keys)),
+           'ffcv_erase_draw_batch_host')
+    return boxes, keys
+
+
+def _erase_fill_ok(fill, keys, planes, pb, itemsize):
+    """The mode of a fill: a pattern of planes x pixel_bytes bytes without keys,
+    a table of ERASE_TABLE entries of the images' itemsize with them."""
+    is_np = isinstance(fill, np.ndarray)
+    size = int(fill.size if is_np else fill.numel())
+    isz = int(fill.itemsize if is_np else fill.element_size())
+    contiguous = bool(fill.flags.c_contiguous) if is_np else fill.is_contiguous()
+    if keys is None:
+        return ERASE_CONSTANT if contiguous and size * isz == planes * pb else None
+    return ERASE_NOISE if contiguous and size == ERASE_TABLE and isz == itemsize and itemsize in (1, 2, 4) else None
+
+
+def erase_batch(images, boxes, fill, keys=None, layout='auto', stream=None, form=None):
+    """RandomErasing's fill in place on a device batch (ffcv_erase_batch): the
+    box ``(y, x, h, w)`` of each sample (device int32 rows, clamped to the
+    image on the device; ``h <= 0`` or ``w <= 0``: nothing) is filled in every
+    channel.  Without ``keys`` ``fill`` is one pixel of every plane, planes x
+    pixel_bytes bytes already in the images' dtype; with ``keys`` (device
+    8-byte integers, one per sample) it is the noise table of 4096 entries of
+    the images' dtype (itemsize 1, 2 or 4) and every element gets the entry
+    its index in the sample selects.  ``images`` is dense with the samples
+    outermost in memory; ``layout`` as in :func:`cutmix_geometry`.  ``form``:
+    diagnostics only, (workgroups per sample and plane, table staged in LDS)."""
+    import torch
+    n = int(images.shape[0]) if images.dim() else 0
+    if images.dim() < 1 or n < 1 or images.numel() < 1 or images.device.type != 'cuda' or \
+            not _dense_like(images, images) or int(images.stride(0)) * n != images.numel():
+        raise TypeError('erase_batch: a dense device tensor with the samples outermost in memory is required, got '
+                        f'shape {tuple(images.shape)} and strides {tuple(images.stride())}')
+    planes, h, w, pb = cutmix_geometry('erase_batch', images, layout)
+    if boxes.dtype != torch.int32 or not boxes.is_contiguous() or boxes.numel() < 4 * n:
+        raise TypeError('erase_batch: boxes must be a contiguous int32 tensor with one (y, x, h, w) per sample')
+    if keys is not None and (keys.element_size() != 8 or not keys.is_contiguous() or keys.numel() < n):
+        raise TypeError('erase_batch: keys must be a contiguous tensor of one 8-byte integer per sample')
+    itemsize = int(images.element_size())
+    mode = _erase_fill_ok(fill, keys, planes, pb, itemsize)
+    if mode is None or isinstance(fill, np.ndarray) or fill.device != images.device:
+        raise TypeError(f'erase_batch: fill must be a contiguous device tensor of {planes} x {pb} bytes (one pixel of '
+                        f'every plane), or with keys a table of {ERASE_TABLE} entries of the images\' dtype')
+    args = (_stream(stream), _p(images), n, planes, h, w, pb, _p(boxes), mode, itemsize, _p(fill), _p(keys))
+    if form is None:
+        _check(lib().ffcv_erase_batch(*args), 'ffcv_erase_batch')
+        return images
+    fn = lib().ffcv_erase_batch_form   # not in ffcv_hip.h: bound on first use
+    fn.restype = c_int
+    fn.argtypes = _SIGS['ffcv_erase_batch'][1] + [c_int, c_int]
+    _check(fn(*args, int(form[0]), int(bool(form[1]))), 'ffcv_erase_batch_form')
+    return images
+
+
+def erase_batch_host(images: np.ndarray, boxes, fill, keys=None, layout='auto', nthreads=1):
+    """The same in place on a writeable C-contiguous numpy array (samples
+    along axis 0); ``fill``: the pattern's bytes, or with ``keys`` the table,
+    an array of the images' itemsize."""
+    if not isinstance(images, np.ndarray) or images.ndim < 1 or images.size < 1 or not images.flags.c_contiguous or \
+            not images.flags.writeable:
+        raise TypeError('erase_batch_host: a writeable C-contiguous array is required')
+    planes, h, w, pb = cutmix_geometry('erase_batch_host', images, layout)
+    n = int(images.shape[0])
+    boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1)
+    if boxes.size < 4 * n:
+        raise TypeError('erase_batch_host: boxes needs one (y, x, h, w) per sample')
+    if keys is not None:
+        keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+        if keys.size < n:
+            raise TypeError('erase_batch_host: keys needs one per sample')
+    fill = np.ascontiguousarray(fill)
+    mode = _erase_fill_ok(fill, keys, planes, pb, int(images.itemsize))
+    if mode is None:
+        raise TypeError(f'erase_batch_host: fill must hold {planes} x {pb} bytes (one pixel of every plane), or with '
+                        f'keys be a table of {ERASE_TABLE} entries of the images\' itemsize')
+    _check(lib().ffcv_erase_batch_host(_p(images), n, planes, h, w, pb, _p(boxes), mode, int(images.itemsize),
+                                       _p(fill), _p(keys), int(max(1, nthreads))), 'ffcv_erase_batch_host')
+    return images
 
 
 def _device_ids(who, sample_ids, poison_ids, n, device):

@@ -12,6 +12,7 @@ from .affine import RandomAffine, RandomRotation
 from .tone import RandomPosterize, RandomAutocontrast, RandomEqualize, RandomInvert
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .cutmix import ImageCutMix, LabelCutMix, ImageMixupCutMix, LabelMixupCutMix
+from .erase import RandomErasing
 from .poison import Poison
 from .replace_label import ReplaceLabel
 from .ops import ToTensor, ToDevice, ToTorchImage, Convert, View
@@ -27,4 +28,4 @@ __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 
            'RandomAffine', 'RandomRotation', 'TrivialAugmentWide',
            'RandomPosterize', 'RandomAutocontrast', 'RandomEqualize', 'RandomInvert',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'ImageCutMix', 'LabelCutMix', 'ImageMixupCutMix',
-           'LabelMixupCutMix', 'Poison', 'ReplaceLabel']
+           'LabelMixupCutMix', 'RandomErasing', 'Poison', 'ReplaceLabel']

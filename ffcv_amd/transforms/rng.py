@@ -11,7 +11,10 @@ draw the same stream twice), 9 grayscale, 10 solarization, 11 blur, 12 hue,
 14 affine (RandomAffine and RandomRotation: seven draws from one stream),
 15 posterize, 16 autocontrast, 17 equalize, 18 invert, 19 sharpness
 (RandomAdjustSharpness) (one draw each), 20 policy (TrivialAugmentWide: three
-draws from one stream).  The device kernels use the same function
+draws from one stream), 21 erase (RandomErasing: apply, then up to ten tries of
+area and aspect ratio, then the box's origin), 22 erase noise (no MT19937: the
+full 64-bit hash is the sample's key into RandomErasing's per-pixel noise,
+transforms/erase.py).  The device kernels use the same function
 (csrc/device_common.h sample_seed).  The reference itself draws from numba's
 per-thread generators seeded from OS entropy (nondeterministic); see
 DESIGN.md "RNG contract".

@@ -1168,6 +1168,64 @@ int ffcv_policy_draw_batch_host(const uint64_t *sample_ids, int batch,
                                 int64_t *aff_coef, uint8_t *sharp_apply,
                                 float *sharp_factor);
 
+/* ------------------------------------------------- random erasing ------ */
+/* RandomErasing.  The draws of sample k, from its own MT19937
+ * under the seeding contract with op id 21: rand() < p first, then up to ten
+ * tries of (area, aspect ratio) for a box of h rows and w columns with
+ * 0 < h < height and 0 < w < width, and the box's origin; the tries are drawn
+ * whether or not the sample applies.
+ *   sample_ids : device uint64[B]
+ *   scale, ratio : host double[2] each (0 <= scale <= 1, ratio > 0, finite)
+ *   boxes      : device int32[B][4] out, (y, x, h, w); h = w = 0: not erased
+ *   keys       : device uint64[B] out, the noise keys (op id 22), or NULL
+ *   status     : device int32[B] out (FFCV_SAMPLE_RNG when the sample's
+ *                MT19937 stream ran out), or NULL
+ * FFCV_EINVAL, before any launch, for a null sample_ids / boxes, batch < 0,
+ * p outside [0, 1], a scale or ratio outside the above, or a height or width
+ * outside 1..32767. */
+int ffcv_erase_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                          uint64_t loader_seed, uint64_t epoch, double p,
+                          const double scale[2], const double ratio[2],
+                          int height, int width, int32_t *boxes,
+                          uint64_t *keys, int32_t *status);
+int ffcv_erase_draw_batch_host(const uint64_t *sample_ids, int batch,
+                               uint64_t loader_seed, uint64_t epoch, double p,
+                               const double scale[2], const double ratio[2],
+                               int height, int width, int32_t *boxes,
+                               uint64_t *keys);
+/* The fill, in place, one launch.  The geometry is ffcv_cutmix_batch's: a
+ * sample is planes x height rows of width * pixel_bytes bytes.  The box
+ * (y, x, h, w) of sample i, clamped to the image here, is filled in every
+ * plane; h <= 0 or w <= 0 leaves the sample alone.  No byte outside
+ * [images, images + n_samples * sample bytes) is written and none outside the
+ * box changes.
+ *   FFCV_ERASE_CONSTANT: fill = planes x pixel_bytes bytes, one pixel of every
+ *     plane, already in the tensor's dtype; itemsize and keys are not used.
+ *   FFCV_ERASE_NOISE: element e of sample i (e: its index in storage order,
+ *     in elements of itemsize bytes) becomes entry
+ *     (splitmix64(keys[i] ^ (e >> 2)) >> (16 * (e & 3) + 4)) & 0xFFF
+ *     of fill, a table of 4096 entries of itemsize (1, 2 or 4) bytes.
+ *   images : device, aligned to itemsize in noise mode, any byte otherwise
+ *   boxes  : device int32[n_samples][4];  keys : device uint64[n_samples]
+ *   fill   : device; the noise table 16-byte aligned
+ * FFCV_EINVAL, before any launch, for a null pointer, a count <= 0,
+ * pixel_bytes outside 1..64 or (noise) no multiple of itemsize, an itemsize
+ * other than 1, 2 or 4, a sample of more than 2^31 - 1 bytes, a mode other
+ * than the two, a misaligned images or table, or more than 2^31 - 1 samples
+ * or 65,535 planes in one launch. */
+enum { FFCV_ERASE_CONSTANT = 0, FFCV_ERASE_NOISE = 1 };
+int ffcv_erase_batch(void *stream, void *images, int64_t n_samples,
+                     int32_t planes, int32_t height, int32_t width,
+                     int32_t pixel_bytes, const int32_t *boxes, int mode,
+                     int32_t itemsize, const void *fill, const uint64_t *keys);
+/* The same on host memory, compiled from the kernel's box and noise
+ * functions, over nthreads threads (one sample at a time each). */
+int ffcv_erase_batch_host(void *images, int64_t n_samples, int32_t planes,
+                          int32_t height, int32_t width, int32_t pixel_bytes,
+                          const int32_t *boxes, int mode, int32_t itemsize,
+                          const void *fill, const uint64_t *keys,
+                          int nthreads);
+
 #ifdef __cplusplus
 }
 #endif
