@@ -20,7 +20,7 @@ SOURCES = ['ffcv_common.hip', 'ffcv_rrc.hip', 'ffcv_jpeg.hip', 'ffcv_host.hip', 
            'ffcv_color.hip', 'ffcv_mixup.hip', 'ffcv_poison.hip', 'ffcv_gather.hip', 'ffcv_rrc_images.hip',
            'ffcv_blur.hip', 'ffcv_hue.hip', 'ffcv_affine.hip', 'ffcv_tone.hip', 'ffcv_standalone.hip',
            'ffcv_simple_aug.hip', 'ffcv_sharpness.hip', 'ffcv_policy.hip', 'ffcv_cutmix.hip',
-           'ffcv_erase.hip']
+           'ffcv_erase.hip', 'ffcv_randaugment.hip']
 HEADERS = ['api_internal.h', 'device_common.h', 'diag_hooks.h', 'color_common.h', 'blur_common.h', 'hue_common.h',
            'affine_common.h', 'tone_common.h', 'poison_common.h', 'jpeg_defs.h', 'jpeg_entropy.h', 'jpeg_idct.h',
            'jpeg_color_resize.h', 'lds_stage.h', 'resize_out.h', 'sharpness_common.h', 'band_tiles.h',

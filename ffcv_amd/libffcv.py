@@ -258,6 +258,13 @@ _SIGS = {
                                  c_int32, c_void_p, c_void_p]),
     'ffcv_erase_batch_host': (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int, c_int32,
                                       c_void_p, c_void_p, c_int]),
+    'ffcv_randaugment_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_int, c_int,
+                                            c_void_p, c_int, c_int] + [c_void_p] * 10),
+    'ffcv_randaugment_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_int, c_int, c_void_p,
+                                                 c_int, c_int] + [c_void_p] * 9),
+    'ffcv_randaugment_lds_bytes': (c_uint64, []),
+    'ffcv_randaugment_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p] +
+                               [c_void_p] * 9),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1156,6 +1163,75 @@ def policy_draw_batch_host(ids, loader_seed, epoch, nbins, table, height, width)
                                              *[_p(out[name]) for name, _, _ in POLICY_ARRAYS]),
            'ffcv_policy_draw_batch_host')
     return out
+
+
+RANDAUGMENT_MAX_OPS = 8  # slots per sample, at most
+
+
+def randaugment_arrays(num_ops):
+    """The arrays ffcv_randaugment_draw_batch fills, in argument order: those
+    of POLICY_ARRAYS, each with a leading slot dimension."""
+    return tuple((name, dt, lambda B, shape=shape: (int(num_ops),) + shape(B)) for name, dt, shape in POLICY_ARRAYS)
+
+
+def randaugment_slot(d, s):
+    """Slot s's slices of the draw's arrays: the arguments of the pixel
+    entries of TrivialAugmentWide for that slot."""
+    return {name: d[name][s] for name, _, _ in POLICY_ARRAYS}
+
+
+def randaugment_draw_batch(ids, loader_seed, epoch, num_ops, nbins, magnitude, table, height, width, out, status=None,
+                           stream=None):
+    """RandAugment's draws of the batch on the device (op id 23) into the
+    device tensors ``out[name]`` of randaugment_arrays(num_ops); table: device
+    float64 (14, nbins)."""
+    if table.numel() != POLICY_NOPS * int(nbins) or table.element_size() != 8 or not table.is_contiguous():
+        raise TypeError(f'randaugment_draw_batch: a contiguous float64 ({POLICY_NOPS}, {nbins}) table is required')
+    _check(lib().ffcv_randaugment_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]), _seed64(loader_seed),
+                                             int(epoch), int(num_ops), int(nbins), int(magnitude), _p(table),
+                                             int(height), int(width),
+                                             *[_p(out[name]) for name, _, _ in POLICY_ARRAYS], _p(status)),
+           'ffcv_randaugment_draw_batch')
+
+
+def randaugment_draw_batch_host(ids, loader_seed, epoch, num_ops, nbins, magnitude, table, height, width):
+    """The same draws on the host: a dict of the randaugment_arrays(num_ops)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.shape != (POLICY_NOPS, int(nbins)):
+        raise TypeError(f'randaugment_draw_batch_host: a float64 ({POLICY_NOPS}, {nbins}) table is required')
+    if not 1 <= int(num_ops) <= RANDAUGMENT_MAX_OPS:
+        raise FFCVError(f'randaugment_draw_batch_host: {num_ops} operations per sample, outside 1 to '
+                        f'{RANDAUGMENT_MAX_OPS}')
+    out = {name: np.empty(shape(ids.size), dt) for name, dt, shape in randaugment_arrays(num_ops)}
+    _check(lib().ffcv_randaugment_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch),
+                                                  int(num_ops), int(nbins), int(magnitude), _p(table), int(height),
+                                                  int(width), *[_p(out[name]) for name, _, _ in POLICY_ARRAYS]),
+           'ffcv_randaugment_draw_batch_host')
+    return out
+
+
+def randaugment_lds_bytes():
+    """6 * H * W of the largest image randaugment_batch takes: the bound of the
+    fused regime, for the dispatch and the tests alike."""
+    return int(lib().ffcv_randaugment_lds_bytes())
+
+
+def randaugment_batch(src, dst, num_ops, mode, fill, d, stream=None):
+    """Every slot of every sample of a dense device uint8 (B, H, W, 3) batch in
+    ONE launch, into ``dst`` (ffcv_randaugment_batch; images up to
+    randaugment_lds_bytes()); d: the device arrays of randaugment_draw_batch."""
+    B, H, W = _u8_batch_dims(src, 'randaugment_batch')
+    if tuple(dst.shape) != tuple(src.shape) or not dst.is_contiguous():
+        raise TypeError(f'randaugment_batch: a contiguous dst of shape {tuple(src.shape)} is required')
+    for name, dt, shape in randaugment_arrays(num_ops):
+        a = d[name]
+        if tuple(a.shape) != shape(B) or a.element_size() != np.dtype(dt).itemsize or not a.is_contiguous():
+            raise TypeError(f'randaugment_batch: {name} must be a contiguous {np.dtype(dt).name} {shape(B)}')
+    f = fill_u8(fill)
+    _check(lib().ffcv_randaugment_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(num_ops), int(mode), _p(f),
+                                        *[_p(d[name]) for name, _, _ in POLICY_ARRAYS]), 'ffcv_randaugment_batch')
+    return dst
 
 
 def tone_tables_host(kind, bits, hists):

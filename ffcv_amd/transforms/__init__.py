@@ -6,7 +6,7 @@ from .color_jitter import (RandomBrightness, RandomContrast, RandomSaturation, R
                            RandomSolarization)
 from .gaussian_blur import GaussianBlur
 from .sharpness import RandomAdjustSharpness
-from .auto_augment import TrivialAugmentWide
+from .auto_augment import TrivialAugmentWide, RandAugment
 from .hue import RandomHue, RandomColorJitter
 from .affine import RandomAffine, RandomRotation
 from .tone import RandomPosterize, RandomAutocontrast, RandomEqualize, RandomInvert
@@ -25,7 +25,7 @@ __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
            'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomAdjustSharpness', 'RandomHue',
            'RandomColorJitter',
-           'RandomAffine', 'RandomRotation', 'TrivialAugmentWide',
+           'RandomAffine', 'RandomRotation', 'TrivialAugmentWide', 'RandAugment',
            'RandomPosterize', 'RandomAutocontrast', 'RandomEqualize', 'RandomInvert',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'ImageCutMix', 'LabelCutMix', 'ImageMixupCutMix',
            'LabelMixupCutMix', 'RandomErasing', 'Poison', 'ReplaceLabel']

@@ -14,7 +14,8 @@ draw the same stream twice), 9 grayscale, 10 solarization, 11 blur, 12 hue,
 draws from one stream), 21 erase (RandomErasing: apply, then up to ten tries of
 area and aspect ratio, then the box's origin), 22 erase noise (no MT19937: the
 full 64-bit hash is the sample's key into RandomErasing's per-pixel noise,
-transforms/erase.py).  The device kernels use the same function
+transforms/erase.py), 23 rand augment (RandAugment: two draws per operation
+slot from one stream).  The device kernels use the same function
 (csrc/device_common.h sample_seed).  The reference itself draws from numba's
 per-thread generators seeded from OS entropy (nondeterministic); see
 DESIGN.md "RNG contract".

@@ -1168,6 +1168,71 @@ int ffcv_policy_draw_batch_host(const uint64_t *sample_ids, int batch,
                                 int64_t *aff_coef, uint8_t *sharp_apply,
                                 float *sharp_factor);
 
+/* ------------------------------------------------- RandAugment --------- */
+/* RandAugment: every sample runs num_ops (1..8) of the 14
+ * operations above in sequence, each on the uint8 result of the one before,
+ * all at the strength of one bin, `magnitude` (0 .. nbins - 1).  Seeding
+ * contract op id 23; one stream per sample, two draws per slot s = 0 ..
+ * num_ops - 1, always both:
+ *   op_s  = min(13, int(rand() * 14))
+ *   neg_s = rand() < 0.5
+ * v = table[op * nbins + magnitude], negated where neg and 1 <= op <= 9; the
+ * table is float64 [14][nbins] as above (device memory for the device entry).
+ * The output arrays are those of ffcv_policy_draw_batch, each with a leading
+ * slot dimension: op uint8[S][B], cj_apply uint8[S][4][B], cj_ratio
+ * float64[S][4][B], tone_apply uint8[S][3][B], tone_bits uint8[S][B],
+ * aff_apply uint8[S][B], aff_coef int64[S][B][6], sharp_apply uint8[S][B],
+ * sharp_factor float32[S][B].  Slot s's slice of each is contiguous and holds
+ * what ffcv_policy_draw_batch would write for that slot's operation, so the
+ * pixel entries above take a slot's slices unchanged.  status: int32[B] or
+ * NULL, per sample (device entry only).
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, num_ops
+ * outside 1..8, nbins outside 2..256, magnitude outside 0..nbins-1, or a
+ * height or width outside 1..32767. */
+int ffcv_randaugment_draw_batch(void *stream, const uint64_t *sample_ids,
+                                int batch, uint64_t loader_seed,
+                                uint64_t epoch, int num_ops, int nbins,
+                                int magnitude, const double *table, int height,
+                                int width, uint8_t *op, uint8_t *cj_apply,
+                                double *cj_ratio, uint8_t *tone_apply,
+                                uint8_t *tone_bits, uint8_t *aff_apply,
+                                int64_t *aff_coef, uint8_t *sharp_apply,
+                                float *sharp_factor, int32_t *status);
+int ffcv_randaugment_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                     uint64_t loader_seed, uint64_t epoch,
+                                     int num_ops, int nbins, int magnitude,
+                                     const double *table, int height,
+                                     int width, uint8_t *op, uint8_t *cj_apply,
+                                     double *cj_ratio, uint8_t *tone_apply,
+                                     uint8_t *tone_bits, uint8_t *aff_apply,
+                                     int64_t *aff_coef, uint8_t *sharp_apply,
+                                     float *sharp_factor);
+/* 6 * height * width of the largest image ffcv_randaugment_batch takes. */
+uint64_t ffcv_randaugment_lds_bytes(void);
+/* The fused pixel pass: every slot of every sample in ONE launch, one
+ * workgroup per image, the image in LDS from the first slot to the last.
+ * src, dst: dense device uint8 [B][height][width][3], out of place (any
+ * overlap is FFCV_EINVAL); src is not written.  mode, fill: as
+ * ffcv_affine_batch.  The arrays are the draw's (device memory).  The kernel
+ * reads slot s's op[s][k] and that operation's argument -- cj_ratio (rows 0,
+ * 1, 2, 3 for brightness, saturation, contrast, solarize), tone_bits,
+ * aff_coef, sharp_factor -- so `op` and the apply arrays must agree, as the
+ * draw writes them; an op code outside 0..13 leaves the image as it is.  The
+ * bytes equal those of the launches above run slot after slot on the slot's
+ * slices; coefficients ffcv_affine_batch refuses give an image of fill here
+ * too, and tone_bits is kept inside 1..8.
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, sizes <= 0,
+ * num_ops outside 1..8, an unknown mode, or 6 * height * width above
+ * ffcv_randaugment_lds_bytes() (the caller runs the slots' launches then). */
+int ffcv_randaugment_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                           int batch, int height, int width, int num_ops,
+                           int mode, const uint8_t *fill, const uint8_t *op,
+                           const uint8_t *cj_apply, const double *cj_ratio,
+                           const uint8_t *tone_apply, const uint8_t *tone_bits,
+                           const uint8_t *aff_apply, const int64_t *aff_coef,
+                           const uint8_t *sharp_apply,
+                           const float *sharp_factor);
+
 /* ------------------------------------------------- random erasing ------ */
 /* RandomErasing.  The draws of sample k, from its own MT19937
  * under the seeding contract with op id 21: rand() < p first, then up to ten
