@@ -265,6 +265,15 @@ _SIGS = {
     'ffcv_randaugment_lds_bytes': (c_uint64, []),
     'ffcv_randaugment_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p] +
                                [c_void_p] * 9),
+    'ffcv_augmix_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_int, c_int, c_double,
+                                       c_int, c_void_p, c_int, c_int] + [c_void_p] * 12),
+    'ffcv_augmix_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_int, c_int, c_double, c_int,
+                                            c_void_p, c_int, c_int] + [c_void_p] * 11),
+    'ffcv_augmix_lds_bytes': (c_uint64, []),
+    'ffcv_augmix_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p] +
+                          [c_void_p] * 11),
+    'ffcv_augmix_mix_batch': (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int]),
+    'ffcv_augmix_mix_batch_host': (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1232,6 +1241,112 @@ def randaugment_batch(src, dst, num_ops, mode, fill, d, stream=None):
     _check(lib().ffcv_randaugment_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(num_ops), int(mode), _p(f),
                                         *[_p(d[name]) for name, _, _ in POLICY_ARRAYS]), 'ffcv_randaugment_batch')
     return dst
+
+
+AUGMIX_MAX_WIDTH, AUGMIX_MAX_DEPTH, AUGMIX_NBINS = 4, 3, 10
+
+
+def augmix_arrays(width):
+    """The arrays ffcv_augmix_draw_batch fills, in argument order: those of
+    randaugment_arrays(3 * width), then the chains' depths and the weights."""
+    return randaugment_arrays(AUGMIX_MAX_DEPTH * int(width)) + (
+        ('depth', np.uint8, lambda B: (int(width), B)), ('weights', np.float32, lambda B: (int(width) + 1, B)))
+
+
+def _augmix_table(table, who):
+    if tuple(table.shape) != (POLICY_NOPS, AUGMIX_NBINS) or table.element_size() != 8 or not table.is_contiguous():
+        raise TypeError(f'{who}: a contiguous float64 ({POLICY_NOPS}, {AUGMIX_NBINS}) table is required')
+
+
+def augmix_draw_batch(ids, loader_seed, epoch, severity, width, chain_depth, alpha, all_ops, table, height, width_px,
+                      out, status=None, stream=None):
+    """AugMix's draws of the batch on the device (op ids 24, 25) into the
+    device tensors ``out[name]`` of augmix_arrays(width); table: device float64
+    (14, 10)."""
+    _augmix_table(table, 'augmix_draw_batch')
+    _check(lib().ffcv_augmix_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]), _seed64(loader_seed), int(epoch),
+                                        int(severity), int(width), int(chain_depth), float(alpha), int(bool(all_ops)),
+                                        _p(table), int(height), int(width_px),
+                                        *[_p(out[name]) for name, _, _ in augmix_arrays(width)], _p(status)),
+           'ffcv_augmix_draw_batch')
+
+
+def augmix_draw_batch_host(ids, loader_seed, epoch, severity, width, chain_depth, alpha, all_ops, table, height,
+                           width_px):
+    """The same draws on the host: a dict of the augmix_arrays(width)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.shape != (POLICY_NOPS, AUGMIX_NBINS):
+        raise TypeError(f'augmix_draw_batch_host: a float64 ({POLICY_NOPS}, {AUGMIX_NBINS}) table is required')
+    if not 1 <= int(width) <= AUGMIX_MAX_WIDTH:
+        raise FFCVError(f'augmix_draw_batch_host: mixture width {width}, outside 1 to {AUGMIX_MAX_WIDTH}')
+    out = {name: np.empty(shape(ids.size), dt) for name, dt, shape in augmix_arrays(width)}
+    _check(lib().ffcv_augmix_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch), int(severity),
+                                             int(width), int(chain_depth), float(alpha), int(bool(all_ops)),
+                                             _p(table), int(height), int(width_px),
+                                             *[_p(out[name]) for name, _, _ in augmix_arrays(width)]),
+           'ffcv_augmix_draw_batch_host')
+    return out
+
+
+def augmix_lds_bytes():
+    """9 * H * W of the largest image augmix_batch takes: the bound of the
+    fused regime, for the dispatch and the tests alike."""
+    return int(lib().ffcv_augmix_lds_bytes())
+
+
+def augmix_batch(src, dst, width, mode, fill, d, stream=None):
+    """Every chain of every sample of a dense device uint8 (B, H, W, 3) batch
+    and the mix in ONE launch, into ``dst`` (ffcv_augmix_batch; images up to
+    augmix_lds_bytes()); d: the device arrays of augmix_draw_batch."""
+    B, H, W = _u8_batch_dims(src, 'augmix_batch')
+    if tuple(dst.shape) != tuple(src.shape) or not dst.is_contiguous():
+        raise TypeError(f'augmix_batch: a contiguous dst of shape {tuple(src.shape)} is required')
+    arrays = augmix_arrays(width)
+    for name, dt, shape in arrays:
+        a = d[name]
+        if tuple(a.shape) != shape(B) or a.element_size() != np.dtype(dt).itemsize or not a.is_contiguous():
+            raise TypeError(f'augmix_batch: {name} must be a contiguous {np.dtype(dt).name} {shape(B)}')
+    f = fill_u8(fill)
+    _check(lib().ffcv_augmix_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(width), int(mode), _p(f),
+                                   *[_p(d[name]) for name, _, _ in arrays]), 'ffcv_augmix_batch')
+    return dst
+
+
+def _augmix_mix_args(orig, results, weights, out, who):
+    B, H, W = _u8_batch_dims(orig, who)
+    width = len(results)
+    if not 1 <= width <= AUGMIX_MAX_WIDTH:
+        raise FFCVError(f'{who}: mixture width {width}, outside 1 to {AUGMIX_MAX_WIDTH}')
+    for a in tuple(results) + (out,):
+        if tuple(a.shape) != tuple(orig.shape):
+            raise TypeError(f'{who}: every batch must have the shape {tuple(orig.shape)}')
+    if tuple(weights.shape) != (width + 1, B):
+        raise TypeError(f'{who}: weights ({width + 1}, {B}) float32 is required')
+    return B, H, W, width, [_p(r) for r in results] + [None] * (AUGMIX_MAX_WIDTH - width)
+
+
+def augmix_mix_batch(orig, results, weights, out, stream=None):
+    """out = the float32 mix of the dense device uint8 (B, H, W, 3) batch
+    ``orig`` and the ``results`` (one batch per chain) at the device float32
+    (width + 1, B) weights, one streaming launch (ffcv_augmix_mix_batch)."""
+    B, H, W, width, r = _augmix_mix_args(orig, results, weights, out, 'augmix_mix_batch')
+    if weights.element_size() != 4 or not all(a.is_contiguous() for a in tuple(results) + (orig, out, weights)):
+        raise TypeError('augmix_mix_batch: contiguous batches and float32 weights are required')
+    _check(lib().ffcv_augmix_mix_batch(_stream(stream), _p(orig), *r, width, _p(weights), _p(out), B, H, W),
+           'ffcv_augmix_mix_batch')
+    return out
+
+
+def augmix_mix_batch_host(orig, results, weights, out, nthreads=1):
+    """The same on C-contiguous numpy arrays."""
+    weights = np.ascontiguousarray(weights, np.float32)
+    B, H, W, width, r = _augmix_mix_args(orig, results, weights, out, 'augmix_mix_batch_host')
+    if not all(a.flags.c_contiguous and a.dtype == np.uint8 for a in tuple(results) + (orig, out)):
+        raise TypeError('augmix_mix_batch_host: C-contiguous uint8 batches are required')
+    _check(lib().ffcv_augmix_mix_batch_host(_p(orig), *r, width, _p(weights), _p(out), B, H, W, int(nthreads)),
+           'ffcv_augmix_mix_batch_host')
+    return out
 
 
 def tone_tables_host(kind, bits, hists):

@@ -1,8 +1,9 @@
-"""TrivialAugmentWide and RandAugment (the reference has
+"""TrivialAugmentWide, RandAugment and AugMix (the reference has
 no augmentation policy: the operations are this project's own, at the strengths
 of the TrivialAugment paper's wide space and of torchvision's RandAugment).
-RandAugment, which runs several operations per sample, is described at its
-class below; this text is TrivialAugmentWide's.
+RandAugment, which runs several operations per sample, and AugMix, which mixes
+several chains of them, are described at their classes below; this text is
+TrivialAugmentWide's.
 
 Every sample runs exactly ONE of 14 operations at a random strength.  It draws
 three values from its own MT19937 under the seeding contract (op id 20),
@@ -324,5 +325,206 @@ class RandAugment(_U8ImageOp):
         _, shape = self.check_u8_images(previous_state)
         if max(shape[0], shape[1]) > 32767:
             raise TypeError(f'RandAugment: images of {shape[0]}x{shape[1]} exceed the supported 32767 per side')
+        self.table = self.table_for(int(shape[0]), int(shape[1]))
+        return self.declare_out_of_place(previous_state)
+
+
+AUGMIX_OPS = tuple(range(1, NUM_OPS))                    # all_ops: every operation but Identity
+AUGMIX_OPS_BASIC = (1, 2, 3, 4, 5, 10, 11, 12, 13)       # ShearX .. Rotate, Posterize .. Equalize
+
+
+def augmix_table(H, W):
+    """float64 (14, 10): AugMix's strength of every operation at every bin
+    b = 0 .. 9 for H x W images, with m = b / 9 (torchvision's ``AugMix``, its
+    _PARAMETER_MAX = 10 bins): shear to 0.3, translation to a third of the
+    side, rotation to 30 degrees, the ratios to 0.9, posterize 4 bits down to
+    1 (4 - round(4 m), torchvision's 0 bits raised to the 1 of ``tone_bits``),
+    solarize 255 down to 0."""
+    b = np.arange(10, dtype=np.int64)
+    m = b.astype(np.float64) / np.float64(9)
+    t = np.zeros((NUM_OPS, 10), np.float64)
+    t[1] = t[2] = np.degrees(np.arctan(np.float64(0.3) * m))
+    t[3] = (int(W) * b) // 27
+    t[4] = (int(H) * b) // 27
+    t[5] = np.float64(30.0) * m
+    t[6] = t[7] = t[8] = t[9] = np.float64(0.9) * m
+    t[10] = np.maximum(1, 4 - (8 * b + 9) // 18)             # 4 - round-half-up(4 m), at least 1: 4 4 3 3 2 2 1 1 1 1
+    t[11] = 255 - (255 * b) // 9
+    return t
+
+
+class AugMix(_U8ImageOp):
+    """AugMix (Hendrycks et al.; the parameters are
+    torchvision's ``AugMix``): ``mixture_width`` independent chains of 1 to 3
+    of the operations of TrivialAugmentWide, each chain from the original
+    image, and the result the float32 convex combination of the original and
+    the chains' results.  Operates on raw arrays (not tensors).
+
+    Every sample draws from two MT19937 streams under the seeding contract.
+    Op id 24, ten values per chain i, always all ten -- ``u_d``, then
+    ``u_op, u_bin, u_neg`` for step j = 0, 1, 2::
+
+        depth_i = chain_depth if chain_depth > 0 else min(3, 1 + int(u_d * 3))
+        op      = OPS[min(n - 1, int(u_op * n))]      (Identity is never drawn)
+        bin     = min(severity - 1, int(u_bin * severity))
+        neg     = u_neg < 0.5
+
+    with the strength ``augmix_table(H, W)[op, bin]``, negated where ``neg`` and
+    the operation is signed.  Op id 25: ``RandomState.standard_gamma(alpha)``
+    for a, b, g_0 .. g_{width-1}, and in float64 ``w_0 = a / (a + b)``,
+    ``w_{i+1} = b / (a + b) * (g_i / sum(g))`` (a Beta and a Dirichlet draw),
+    each rounded once to float32.  Per byte, in float32 with every product and
+    sum rounded on its own, ``acc = w_0 x``, then ``acc += w_{i+1} y_i`` chain
+    after chain, and ``min(255, rint(acc))``, half to even (torchvision
+    truncates, which darkens an unchanged image by one level whenever the
+    float32 weights sum to just under 1).
+
+    On device tensors it is the draw's launches and, for images up to 64 x 64
+    (``libffcv.augmix_lds_bytes()``), ONE pixel launch (ffcv_augmix_batch);
+    beyond, per chain a copy and the rounds of RandAugment, then one streaming
+    launch for the mix (ffcv_augmix_mix_batch).  On host arrays it is the host
+    twins of the rounds and of the mix.
+
+    Parameters
+    ----------
+    severity : int
+        The strongest bin drawn, in [1, 10].
+    mixture_width : int
+        Chains per image, in [1, 4].
+    chain_depth : int
+        Operations per chain, in [1, 3], or -1: 1 to 3 at random per chain.
+    alpha : float
+        The shape of the Beta and Dirichlet draws, in [0.01, 100].
+    all_ops : bool
+        All 13 operations, or without Brightness, Color, Contrast, Sharpness.
+    interpolation : str
+        'nearest' or 'bilinear', for the geometric operations.
+    fill : int or Tuple[int, int, int]
+        The colour outside the source image, for the geometric operations.
+    """
+    op_id = 24
+    weight_op_id = 25
+
+    def __init__(self, severity=3, mixture_width=3, chain_depth=-1, alpha=1.0, all_ops=True, interpolation='nearest',
+                 fill=(0, 0, 0)):
+        super().__init__()
+        name = 'AugMix'
+
+        def is_int(v):
+            return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+        if not is_int(severity) or not 1 <= severity <= 10:
+            raise ValueError(f'{name}: severity must be an int in [1, 10], got {severity!r}')
+        if not is_int(mixture_width) or not 1 <= mixture_width <= 4:
+            raise ValueError(f'{name}: mixture_width must be an int in [1, 4], got {mixture_width!r}')
+        if not is_int(chain_depth) or not (chain_depth == -1 or 1 <= chain_depth <= 3):
+            raise ValueError(f'{name}: chain_depth must be -1 or an int in [1, 3], got {chain_depth!r}')
+        if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0.01 <= alpha <= 100:
+            raise ValueError(f'{name}: alpha must be a number in [0.01, 100], got {alpha!r}')
+        if not isinstance(all_ops, bool):
+            raise ValueError(f'{name}: all_ops must be a bool, got {all_ops!r}')
+        if not isinstance(interpolation, str) or interpolation not in _MODES:
+            raise ValueError(f"{name}: interpolation must be 'bilinear' or 'nearest', got {interpolation!r}")
+        try:
+            f = np.asarray(fill)
+            ok = f.dtype.kind in 'iuf' and f.size in (1, 3) and np.isfinite(f).all()
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f'{name}: fill must be a number or an RGB triple, got {fill!r}')
+        self.severity, self.mixture_width, self.chain_depth = int(severity), int(mixture_width), int(chain_depth)
+        self.alpha, self.all_ops = float(alpha), all_ops
+        self.interpolation = interpolation
+        self.fill = f
+        self.table = None          # built in declare_state_and_memory, where the shape is known
+        self._tables = {}
+        self._dev_tables = {}
+
+    def table_for(self, H, W):
+        """The value table of H x W images, built once per shape."""
+        t = self._tables.get((H, W))
+        if t is None:
+            t = self._tables[(H, W)] = augmix_table(H, W)
+        return t
+
+    def device_table(self, H, W, device):
+        t = self._dev_tables.get((H, W, device))
+        if t is None:
+            t = self._dev_tables[(H, W, device)] = ch.from_numpy(self.table_for(H, W)).to(device)
+        return t
+
+    def generate_code(self) -> Callable:
+        from .. import libffcv as L
+        width, mode, fill = self.mixture_width, _MODES[self.interpolation], fill_u8(self.fill)
+        draw = (self.severity, width, self.chain_depth, self.alpha, self.all_ops)
+        rounds = self.chain_depth if self.chain_depth > 0 else L.AUGMIX_MAX_DEPTH
+        key = ('aug_mix', id(self))
+
+        def chain_buffers(i, result, spare):
+            """Where chain i's copy of the input goes, then where each round
+            writes: the last one into ``result``."""
+            order = [spare, result] if rounds % 2 else [result, spare]
+            return [order[r % 2] for r in range(rounds + 1)]
+
+        def device(ctx, images, out):
+            B, H, W = (int(x) for x in images.shape[:3])
+            d = {}
+            for name, dt, shape in L.augmix_arrays(width):
+                shp = shape(B)
+                n = int(np.prod(shp))
+                d[name] = ctx.device_buffer(key + (name,), int(np.prod(shape(ctx.batch_size))),
+                                            getattr(ch, np.dtype(dt).name))[:n].view(shp)
+            L.augmix_draw_batch(ctx.batch_ids, ctx.loader_seed, ctx.epoch, *draw, self.device_table(H, W, images.device),
+                                H, W, d, None, ctx.stream)
+            if 9 * H * W <= L.augmix_lds_bytes():
+                L.augmix_batch(images, out, width, mode, fill, d, ctx.stream)
+                return
+            # per chain a copy of the input and RandAugment's rounds, then the streaming mix
+            cj_ws = tone_ws = None
+            if H * W * 3 > L.color_jitter_lds_bytes():
+                cj_ws = ctx.device_buffer(key + ('cj_ws',), ctx.batch_size, ch.int64)[:B]
+            if H * W * 3 > L.tone_lds_bytes():
+                tone_ws = ctx.device_buffer(key + ('tone_ws',), 768 * ctx.batch_size, ch.int32)[:768 * B]
+
+            def batch_buffer(name):
+                return ctx.device_buffer(key + (name,), ctx.batch_size * H * W * 3,
+                                         ch.uint8)[:B * H * W * 3].view(images.shape)
+            results = [batch_buffer(('result', i)) for i in range(width)]
+            spare = batch_buffer('spare')
+            for i in range(width):
+                bufs = chain_buffers(i, results[i], spare)
+                bufs[0].copy_(images)        # (the Loader runs this code with ctx.stream current)
+                for r in range(rounds):
+                    cur, nxt = bufs[r], bufs[r + 1]
+                    a = L.randaugment_slot(d, L.AUGMIX_MAX_DEPTH * i + r)
+                    L.color_jitter_batch(cur, _CJ_STEPS, a['cj_apply'][:3], a['cj_ratio'][:3], cj_ws, ctx.stream)
+                    L.color_jitter_batch(cur, _SOLARIZE_STEPS, a['cj_apply'][3:], a['cj_ratio'][3:], None,
+                                         ctx.stream)
+                    L.tone_batch_bits(cur, _TONE_STEPS, a['tone_apply'], a['tone_bits'], tone_ws, ctx.stream)
+                    L.affine_batch(cur, nxt, mode, fill, a['aff_apply'], a['aff_coef'], 0, ctx.stream)
+                    L.sharpness_batch(cur, nxt, a['sharp_apply'], a['sharp_factor'], 0, ctx.stream)
+            L.augmix_mix_batch(images, results, d['weights'], out, ctx.stream)
+
+        def host(seed, epoch, ids, src, out_np, nthreads):
+            H, W = src.shape[1:3]
+            d = L.augmix_draw_batch_host(ids, seed, epoch, *draw, self.table_for(H, W), H, W)
+            results, spare = [np.empty_like(src) for _ in range(width)], np.empty_like(src)
+            for i in range(width):
+                bufs = chain_buffers(i, results[i], spare)
+                bufs[0][...] = src
+                for r in range(rounds):
+                    cur, nxt = bufs[r], bufs[r + 1]
+                    a = L.randaugment_slot(d, L.AUGMIX_MAX_DEPTH * i + r)
+                    L.color_jitter_batch_host(cur, _CJ_STEPS, a['cj_apply'][:3], a['cj_ratio'][:3])
+                    L.color_jitter_batch_host(cur, _SOLARIZE_STEPS, a['cj_apply'][3:], a['cj_ratio'][3:])
+                    L.tone_batch_bits_host(cur, _TONE_STEPS, a['tone_apply'], a['tone_bits'])
+                    L.affine_batch_host(cur, nxt, mode, fill, a['aff_apply'], a['aff_coef'], nthreads=nthreads)
+                    L.sharpness_batch_host(cur, nxt, a['sharp_apply'], a['sharp_factor'], nthreads=nthreads)
+            L.augmix_mix_batch_host(src, results, d['weights'], out_np[:len(src)], nthreads)
+        return self.out_of_place_code(device, host)
+
+    def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
+        _, shape = self.check_u8_images(previous_state)
+        if max(shape[0], shape[1]) > 32767:
+            raise TypeError(f'AugMix: images of {shape[0]}x{shape[1]} exceed the supported 32767 per side')
         self.table = self.table_for(int(shape[0]), int(shape[1]))
         return self.declare_out_of_place(previous_state)

@@ -15,7 +15,9 @@ draws from one stream), 21 erase (RandomErasing: apply, then up to ten tries of
 area and aspect ratio, then the box's origin), 22 erase noise (no MT19937: the
 full 64-bit hash is the sample's key into RandomErasing's per-pixel noise,
 transforms/erase.py), 23 rand augment (RandAugment: two draws per operation
-slot from one stream).  The device kernels use the same function
+slot from one stream), 24 aug mix chains (AugMix: ten draws per chain from one
+stream), 25 aug mix weights (AugMix: the Beta and Dirichlet gammas, legacy
+RandomState.standard_gamma, a stream of varying length).  The device kernels use the same function
 (csrc/device_common.h sample_seed).  The reference itself draws from numba's
 per-thread generators seeded from OS entropy (nondeterministic); see
 DESIGN.md "RNG contract".

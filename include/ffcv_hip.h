@@ -1233,6 +1233,88 @@ int ffcv_randaugment_batch(void *stream, const uint8_t *src, uint8_t *dst,
                            const uint8_t *sharp_apply,
                            const float *sharp_factor);
 
+/* ------------------------------------------------- AugMix -------------- */
+/* AugMix: every sample runs mixture_width (1..4) chains of
+ * 1..3 of the operations above, each chain from the original image, and
+ * leaves as  w_0 x + w_1 y_0 + .. + w_width y_{width-1}  in float32, every
+ * product and sum rounded on its own, then min(255, rint()) (half to even).
+ * Chain draws, op id 24, one stream per sample, ten values per chain i, always
+ * all ten: u_d, then (u_op, u_bin, u_neg) for step j = 0..2:
+ *   depth_i = chain_depth if positive, else min(3, 1 + int(u_d * 3))
+ *   op   = OPS[min(n - 1, int(u_op * n))]: the codes 1..13 (n = 13) with
+ *          all_ops, else 1..5 and 10..13 (n = 9); Identity is never drawn
+ *   bin  = min(severity - 1, int(u_bin * severity)), neg = u_neg < 0.5
+ * v = table[op * 10 + bin] (float64 [14][10]), negated where neg and 1 <= op
+ * <= 9.  Slot 3 i + j of the arrays of ffcv_randaugment_draw_batch (S = 3 *
+ * mixture_width slots) holds step j of chain i, Identity for j >= depth_i;
+ * depth: uint8 [mixture_width][B].
+ * Weight draws, op id 25, a stream of its own: numpy's legacy
+ * RandomState.standard_gamma(alpha) for a, b, g_0 .. g_{width-1}, then in
+ * float64 w_0 = a / (a + b), w_{i+1} = (b / (a + b)) * (g_i / (((g_0 + g_1) +
+ * g_2) + g_3)), each rounded once to float32; weights: float32
+ * [mixture_width + 1][B].  A sample whose stream runs out, or with a sum that
+ * is 0 or not finite, gets (1, 0, .., 0) and FFCV_SAMPLE_RNG in status (int32
+ * [B] or NULL; the host entry returns FFCV_EINVAL after writing every sample).
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, severity
+ * outside 1..10, mixture_width outside 1..4, chain_depth other than -1, 1, 2,
+ * 3, alpha outside [0.01, 100], or a height or width outside 1..32767. */
+int ffcv_augmix_draw_batch(void *stream, const uint64_t *sample_ids, int batch,
+                           uint64_t loader_seed, uint64_t epoch, int severity,
+                           int mixture_width, int chain_depth, double alpha,
+                           int all_ops, const double *table, int height,
+                           int width, uint8_t *op, uint8_t *cj_apply,
+                           double *cj_ratio, uint8_t *tone_apply,
+                           uint8_t *tone_bits, uint8_t *aff_apply,
+                           int64_t *aff_coef, uint8_t *sharp_apply,
+                           float *sharp_factor, uint8_t *depth, float *weights,
+                           int32_t *status);
+int ffcv_augmix_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                uint64_t loader_seed, uint64_t epoch,
+                                int severity, int mixture_width,
+                                int chain_depth, double alpha, int all_ops,
+                                const double *table, int height, int width,
+                                uint8_t *op, uint8_t *cj_apply,
+                                double *cj_ratio, uint8_t *tone_apply,
+                                uint8_t *tone_bits, uint8_t *aff_apply,
+                                int64_t *aff_coef, uint8_t *sharp_apply,
+                                float *sharp_factor, uint8_t *depth,
+                                float *weights);
+/* 9 * height * width of the largest image ffcv_augmix_batch takes. */
+uint64_t ffcv_augmix_lds_bytes(void);
+/* The fused pixel pass: every chain of every sample and the mix in ONE launch,
+ * one workgroup per image; the original stays in LDS, the chains run there,
+ * the mix is accumulated in registers.  Arguments as ffcv_randaugment_batch,
+ * the arrays with 3 * mixture_width slots; chain i runs the first depth[i][k]
+ * (kept inside 1..3) of its slots.
+ * FFCV_EINVAL, before any launch, as ffcv_randaugment_batch, for a
+ * mixture_width outside 1..4, or 9 * height * width above
+ * ffcv_augmix_lds_bytes() (the caller runs the chains' launches and
+ * ffcv_augmix_mix_batch then). */
+int ffcv_augmix_batch(void *stream, const uint8_t *src, uint8_t *dst, int batch,
+                      int height, int width, int mixture_width, int mode,
+                      const uint8_t *fill, const uint8_t *op,
+                      const uint8_t *cj_apply, const double *cj_ratio,
+                      const uint8_t *tone_apply, const uint8_t *tone_bits,
+                      const uint8_t *aff_apply, const int64_t *aff_coef,
+                      const uint8_t *sharp_apply, const float *sharp_factor,
+                      const uint8_t *depth, const float *weights);
+/* The mix alone, streaming: out = the mix of orig and the first mixture_width
+ * of r0..r3 (the others are not read), all dense uint8 [B][height][width][3]
+ * at any alignment, out overlapping none of them; one launch, 16 bytes of out
+ * per thread.  The host twin runs the same arithmetic over nthreads threads.
+ * FFCV_EINVAL for a null pointer that is read, batch < 0, sizes <= 0, a
+ * mixture_width outside 1..4 or an overlap. */
+int ffcv_augmix_mix_batch(void *stream, const uint8_t *orig, const uint8_t *r0,
+                          const uint8_t *r1, const uint8_t *r2,
+                          const uint8_t *r3, int mixture_width,
+                          const float *weights, uint8_t *out, int batch,
+                          int height, int width);
+int ffcv_augmix_mix_batch_host(const uint8_t *orig, const uint8_t *r0,
+                               const uint8_t *r1, const uint8_t *r2,
+                               const uint8_t *r3, int mixture_width,
+                               const float *weights, uint8_t *out, int batch,
+                               int height, int width, int nthreads);
+
 /* ------------------------------------------------- random erasing ------ */
 /* RandomErasing.  The draws of sample k, from its own MT19937
  * under the seeding contract with op id 21: rand() < p first, then up to ten
