@@ -1,5 +1,7 @@
 // ffcv_randaugment.hip -- RandAugment: the draws (op id 23)
 // and the fused pixel pass for images up to 64 x 64, with the draws' host twin.
+// (The fused pass for larger images, up to 224 x 224, from a single LDS buffer:
+// ffcv_randaugment_large.hip.)
 //
 // A sample runs num_ops operations of the 14 of s24 in sequence, each on the
 // uint8 result of the one before, all at one fixed strength bin.

@@ -265,6 +265,10 @@ _SIGS = {
     'ffcv_randaugment_lds_bytes': (c_uint64, []),
     'ffcv_randaugment_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p] +
                                [c_void_p] * 9),
+    'ffcv_randaugment_large_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                             c_void_p] + [c_void_p] * 9),
+    'ffcv_randaugment_large_fits': (c_int, [c_int, c_int]),
+    'ffcv_randaugment_large_min_bytes': (c_uint64, []),
     'ffcv_augmix_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_int, c_int, c_double,
                                        c_int, c_void_p, c_int, c_int] + [c_void_p] * 12),
     'ffcv_augmix_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_int, c_int, c_int, c_double, c_int,
@@ -1226,21 +1230,46 @@ def randaugment_lds_bytes():
     return int(lib().ffcv_randaugment_lds_bytes())
 
 
+def _randaugment_pixels(entry, src, dst, num_ops, mode, fill, d, stream):
+    who = entry[len('ffcv_'):]
+    B, H, W = _u8_batch_dims(src, who)
+    if tuple(dst.shape) != tuple(src.shape) or not dst.is_contiguous():
+        raise TypeError(f'{who}: a contiguous dst of shape {tuple(src.shape)} is required')
+    for name, dt, shape in randaugment_arrays(num_ops):
+        a = d[name]
+        if tuple(a.shape) != shape(B) or a.element_size() != np.dtype(dt).itemsize or not a.is_contiguous():
+            raise TypeError(f'{who}: {name} must be a contiguous {np.dtype(dt).name} {shape(B)}')
+    f = fill_u8(fill)
+    _check(getattr(lib(), entry)(_stream(stream), _p(src), _p(dst), B, H, W, int(num_ops), int(mode), _p(f),
+                                 *[_p(d[name]) for name, _, _ in POLICY_ARRAYS]), entry)
+    return dst
+
+
 def randaugment_batch(src, dst, num_ops, mode, fill, d, stream=None):
     """Every slot of every sample of a dense device uint8 (B, H, W, 3) batch in
     ONE launch, into ``dst`` (ffcv_randaugment_batch; images up to
     randaugment_lds_bytes()); d: the device arrays of randaugment_draw_batch."""
-    B, H, W = _u8_batch_dims(src, 'randaugment_batch')
-    if tuple(dst.shape) != tuple(src.shape) or not dst.is_contiguous():
-        raise TypeError(f'randaugment_batch: a contiguous dst of shape {tuple(src.shape)} is required')
-    for name, dt, shape in randaugment_arrays(num_ops):
-        a = d[name]
-        if tuple(a.shape) != shape(B) or a.element_size() != np.dtype(dt).itemsize or not a.is_contiguous():
-            raise TypeError(f'randaugment_batch: {name} must be a contiguous {np.dtype(dt).name} {shape(B)}')
-    f = fill_u8(fill)
-    _check(lib().ffcv_randaugment_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(num_ops), int(mode), _p(f),
-                                        *[_p(d[name]) for name, _, _ in POLICY_ARRAYS]), 'ffcv_randaugment_batch')
-    return dst
+    return _randaugment_pixels('ffcv_randaugment_batch', src, dst, num_ops, mode, fill, d, stream)
+
+
+def randaugment_large_fits(height, width):
+    """Does randaugment_large_batch take images of this shape?  True for every
+    shape up to 224 x 224; the one predicate of the entry's guard, the dispatch
+    and the tests."""
+    return bool(lib().ffcv_randaugment_large_fits(int(height), int(width)))
+
+
+def randaugment_large_min_bytes():
+    """3 * H * W from which the dispatch sends a shape that fits to
+    randaugment_large_batch (the entry itself takes smaller ones)."""
+    return int(lib().ffcv_randaugment_large_min_bytes())
+
+
+def randaugment_large_batch(src, dst, num_ops, mode, fill, d, stream=None):
+    """randaugment_batch for images beyond its regime, up to 224 x 224
+    (ffcv_randaugment_large_batch: ONE launch, one image buffer in LDS; the
+    shapes of randaugment_large_fits)."""
+    return _randaugment_pixels('ffcv_randaugment_large_batch', src, dst, num_ops, mode, fill, d, stream)
 
 
 AUGMIX_MAX_WIDTH, AUGMIX_MAX_DEPTH, AUGMIX_NBINS = 4, 3, 10

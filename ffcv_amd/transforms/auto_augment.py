@@ -201,9 +201,11 @@ class RandAugment(_U8ImageOp):
     On device tensors it is one draw launch (ffcv_randaugment_draw_batch) and,
     for images up to 64 x 64 (``libffcv.randaugment_lds_bytes()``), ONE pixel
     launch that keeps the image in LDS across its slots (ffcv_randaugment_batch);
-    beyond, slot after slot, the five pixel launches of TrivialAugmentWide on
-    the slot's slices of the draws.  On host arrays it is the host twins of
-    those launches.
+    from ``libffcv.randaugment_large_min_bytes()`` bytes per image up to 224 x 224
+    (``libffcv.randaugment_large_fits``) ONE launch too, with a single image
+    buffer in LDS (ffcv_randaugment_large_batch); otherwise, slot after slot,
+    the five pixel launches of TrivialAugmentWide on the slot's slices of the
+    draws.  On host arrays it is the host twins of those launches.
 
     Parameters
     ----------
@@ -282,6 +284,9 @@ class RandAugment(_U8ImageOp):
                                      self.device_table(H, W, images.device), H, W, d, None, ctx.stream)
             if 6 * H * W <= L.randaugment_lds_bytes():
                 L.randaugment_batch(images, out, S, mode, fill, d, ctx.stream)
+                return
+            if 3 * H * W >= L.randaugment_large_min_bytes() and L.randaugment_large_fits(H, W):
+                L.randaugment_large_batch(images, out, S, mode, fill, d, ctx.stream)
                 return
             # rounds: slot after slot the launches of TrivialAugmentWide, from the current buffer into the next
             cj_ws = tone_ws = None

@@ -1232,6 +1232,31 @@ int ffcv_randaugment_batch(void *stream, const uint8_t *src, uint8_t *dst,
                            const uint8_t *aff_apply, const int64_t *aff_coef,
                            const uint8_t *sharp_apply,
                            const float *sharp_factor);
+/* The same pass for images beyond that regime, up to 224 x 224: ONE launch,
+ * one workgroup per image, the image in a single LDS buffer (an operation
+ * that moves pixels keeps its result in registers across a barrier).
+ * Arguments, bytes and guards are ffcv_randaugment_batch's; the shapes it
+ * takes are those of ffcv_randaugment_large_fits(height, width): non-zero for
+ * every shape with 3 * height * width <= 150,528 (224 x 224, and every height
+ * and width up to 224) but tall thin ones whose rows of 3 * width bytes, each
+ * rounded up to a multiple of 4, sum to more than 151,552.  Any other shape is
+ * FFCV_EINVAL before any launch.  ffcv_randaugment_large_min_bytes() is the
+ * lower edge, in bytes of 3 * height * width, from which a caller that
+ * dispatches between this entry and the slots' launches should prefer this
+ * one (the measured break-even; the entry itself takes smaller shapes). */
+int ffcv_randaugment_large_fits(int height, int width);
+uint64_t ffcv_randaugment_large_min_bytes(void);
+int ffcv_randaugment_large_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                                 int batch, int height, int width, int num_ops,
+                                 int mode, const uint8_t *fill,
+                                 const uint8_t *op, const uint8_t *cj_apply,
+                                 const double *cj_ratio,
+                                 const uint8_t *tone_apply,
+                                 const uint8_t *tone_bits,
+                                 const uint8_t *aff_apply,
+                                 const int64_t *aff_coef,
+                                 const uint8_t *sharp_apply,
+                                 const float *sharp_factor);
 
 /* ------------------------------------------------- AugMix -------------- */
 /* AugMix: every sample runs mixture_width (1..4) chains of

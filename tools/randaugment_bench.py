@@ -5,11 +5,15 @@ TrivialAugmentWide on the slot's slices of the same arrays) and next to a
 device-to-device copy.
 
     python tools/randaugment_bench.py [--reps 60] [--rounds 3] [--warmup 10] [--ring-mb 640] [--num-ops 2]
+                                      [--shapes 128x128,224x224]
 
-Shapes: 512 x 32 x 32 and 256 x 64 x 64 (the edge of the fused regime),
-uniformly random pixels, num_ops = 2, magnitude 9 of 31 bins, nearest.
+Shapes: 512 x 32 x 32 and 256 x 64 x 64 (the edge of the small fused regime),
+then 256 x 128 x 128, 160 x 160, 192 x 192 and 224 x 224 (the large fused
+kernel, whatever the dispatch's lower edge is); uniformly random pixels,
+num_ops = 2, magnitude 9 of 31 bins, nearest.
 
-  fused   ffcv_randaugment_draw_batch, ffcv_randaugment_batch
+  fused   ffcv_randaugment_draw_batch, then ffcv_randaugment_batch up to 64 x 64,
+          ffcv_randaugment_large_batch beyond
   rounds  ffcv_randaugment_draw_batch, then per slot two ffcv_color_jitter_batch,
           ffcv_tone_batch_bits, ffcv_affine_batch and ffcv_sharpness_batch, as the
           operation runs them beyond the fused regime (the baseline: existing kernels)
@@ -34,7 +38,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CASES = ((512, 32, 32), (256, 64, 64))
+CASES = ((512, 32, 32), (256, 64, 64), (256, 128, 128), (256, 160, 160), (256, 192, 192), (256, 224, 224))
 CJ_STEPS, SOLARIZE_STEPS, TONE_STEPS = (1, 3, 2), (5,), (1, 2, 3)
 NBINS, MAGNITUDE, SEED = 31, 9, 3
 
@@ -46,6 +50,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--ring-mb', type=int, default=640)
     ap.add_argument('--num-ops', type=int, default=2)
+    ap.add_argument('--shapes', help='only these shapes of the list, as HxW,HxW')
     args = ap.parse_args()
     import torch as ch
     from ffcv_amd import _build, libffcv as L
@@ -59,7 +64,11 @@ def main():
     variants = ('fused', 'rounds', 'd2d')
     mode, fill = L.AFFINE_NEAREST, (0, 0, 0)
     for B, H, W in CASES:
-        assert 6 * H * W <= L.randaugment_lds_bytes()
+        if args.shapes and f'{H}x{W}' not in args.shapes.split(','):
+            continue
+        small = 6 * H * W <= L.randaugment_lds_bytes()
+        assert small or L.randaugment_large_fits(H, W)
+        fused = L.randaugment_batch if small else L.randaugment_large_batch
         nbytes = B * H * W * 3
         nring = max(2, -(-args.ring_mb * (1 << 20) // nbytes))
         rings = {name: [ch.empty((B, H, W, 3), dtype=ch.uint8, device=dev) for _ in range(nring)]
@@ -77,6 +86,9 @@ def main():
         d = {name: ch.empty(shape(B), dtype=getattr(ch, np.dtype(dt).name), device=dev)
              for name, dt, shape in L.randaugment_arrays(S)}
         spare = [ch.empty((B, H, W, 3), dtype=ch.uint8, device=dev) for _ in range(min(2, S - 1))]
+        # the workspaces the operation gives the rounds beyond their entries' LDS regimes
+        cj_ws = ch.empty(B, dtype=ch.int64, device=dev) if H * W * 3 > L.color_jitter_lds_bytes() else None
+        tone_ws = ch.empty(768 * B, dtype=ch.int32, device=dev) if H * W * 3 > L.tone_lds_bytes() else None
 
         def run_rounds(x, dst):
             L.randaugment_draw_batch(ids, SEED, 0, S, NBINS, MAGNITUDE, table, H, W, d)
@@ -84,9 +96,9 @@ def main():
             for s in range(S):
                 nxt = dst if s == S - 1 else spare[s % 2]
                 a = L.randaugment_slot(d, s)
-                L.color_jitter_batch(cur, CJ_STEPS, a['cj_apply'][:3], a['cj_ratio'][:3])
+                L.color_jitter_batch(cur, CJ_STEPS, a['cj_apply'][:3], a['cj_ratio'][:3], cj_ws)
                 L.color_jitter_batch(cur, SOLARIZE_STEPS, a['cj_apply'][3:], a['cj_ratio'][3:])
-                L.tone_batch_bits(cur, TONE_STEPS, a['tone_apply'], a['tone_bits'])
+                L.tone_batch_bits(cur, TONE_STEPS, a['tone_apply'], a['tone_bits'], tone_ws)
                 L.affine_batch(cur, nxt, mode, fill, a['aff_apply'], a['aff_coef'])
                 L.sharpness_batch(cur, nxt, a['sharp_apply'], a['sharp_factor'])
                 cur = nxt
@@ -97,10 +109,11 @@ def main():
                 dst.copy_(src)
             elif name == 'fused':
                 L.randaugment_draw_batch(ids, SEED, 0, S, NBINS, MAGNITUDE, table, H, W, d)
-                L.randaugment_batch(src, dst, S, mode, fill, d)
+                fused(src, dst, S, mode, fill, d)
             else:
                 run_rounds(rings['rounds'][i % nring], dst)
-        res = {'unit': 'us', 'batch': B, 'shape': f'{H}x{W}', 'num_ops': S, 'bytes': 2 * nbytes, 'ring': nring,
+        res = {'unit': 'us', 'batch': B, 'kernel': 'small' if small else 'large', 'shape': f'{H}x{W}', 'num_ops': S,
+               'bytes': 2 * nbytes, 'ring': nring,
                'config': f'{args.reps} launches x {args.rounds} rounds'}
         # both paths compute the same bytes, which are the host twins'
         before = rings['src'][0].clone()
