@@ -96,7 +96,7 @@ inline bool run_tiling(const char *who, int batch, uint64_t npx, uint32_t lds_by
 template <class K, class... A>
 int launch_draw(const char *name, K kernel, void *stream, int batch, A... args) {
   if (batch == 0) return FFCV_OK;
-  hipLaunchKernelGGL(kernel, dim3((batch + 63) / 64), dim3(64), 0, as_stream(stream), args...);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(((uint64_t)batch + 63) / 64)), dim3(64), 0, as_stream(stream), args...);
   FFCV_LAUNCH_CHECK(name);
   return FFCV_OK;
 }

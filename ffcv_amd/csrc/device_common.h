@@ -241,15 +241,15 @@ FFCV_HD int draw_part(int part, int k, uint64_t id, uint32_t H, uint32_t W, cons
     } else {
       center_crop(H, W, p.center_ratio, c);
     }
-    crops[4 * k + 0] = c[0];
-    crops[4 * k + 1] = c[1];
-    crops[4 * k + 2] = c[2];
-    crops[4 * k + 3] = c[3];
+    crops[4 * (size_t)k + 0] = c[0];
+    crops[4 * (size_t)k + 1] = c[1];
+    crops[4 * (size_t)k + 2] = c[2];
+    crops[4 * (size_t)k + 3] = c[3];
     return err;
   }
   if (part == 1 && cut && p.cutout_size > 0) {
-    cut[2 * k + 0] = (int32_t)mt_randint(m, p.out_h - p.cutout_size + 1);
-    cut[2 * k + 1] = (int32_t)mt_randint(m, p.out_w - p.cutout_size + 1);
+    cut[2 * (size_t)k + 0] = (int32_t)mt_randint(m, p.out_h - p.cutout_size + 1);
+    cut[2 * (size_t)k + 1] = (int32_t)mt_randint(m, p.out_w - p.cutout_size + 1);
     return m.err;
   }
   if (part == 2 && flips) {
@@ -264,8 +264,8 @@ FFCV_HD int draw_part(int part, int k, uint64_t id, uint32_t H, uint32_t W, cons
 FFCV_HD int draw_translate(int k, uint64_t id, uint64_t loader_seed, uint64_t epoch, int padding, int32_t *yx) {
   DevMT m;
   mt_init(m, sample_seed(loader_seed, epoch, id, 4));
-  yx[2 * k + 0] = (int32_t)mt_randint(m, 2 * (int64_t)padding + 1);
-  yx[2 * k + 1] = (int32_t)mt_randint(m, 2 * (int64_t)padding + 1);
+  yx[2 * (size_t)k + 0] = (int32_t)mt_randint(m, 2 * (int64_t)padding + 1);
+  yx[2 * (size_t)k + 1] = (int32_t)mt_randint(m, 2 * (int64_t)padding + 1);
   return m.err;
 }
 

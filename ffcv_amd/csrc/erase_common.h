@@ -86,10 +86,10 @@ FFCV_HD int draw_erase(int k, uint64_t id, uint64_t loader_seed, uint64_t epoch,
     }
   }
   if (!apply) y = x = bh = bw = 0;
-  boxes[4 * k] = y;
-  boxes[4 * k + 1] = x;
-  boxes[4 * k + 2] = bh;
-  boxes[4 * k + 3] = bw;
+  boxes[4 * (size_t)k] = y;
+  boxes[4 * (size_t)k + 1] = x;
+  boxes[4 * (size_t)k + 2] = bh;
+  boxes[4 * (size_t)k + 3] = bw;
   if (keys) keys[k] = erase_key(loader_seed, epoch, id);
   return m.err;
 }

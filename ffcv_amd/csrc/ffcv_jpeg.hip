@@ -355,6 +355,10 @@ static int check_common(const char *fn, ffcv_jpeg_ctx *c, const uint8_t *base, c
     ffcv::set_error("%s: invalid arguments", fn);
     return FFCV_EINVAL;
   }
+  if (batch > 65535) {  // the colour / resize kernels take the image from blockIdx.y
+    ffcv::set_error("%s: batch %d exceeds the 65535 images of one launch", fn, batch);
+    return FFCV_EINVAL;
+  }
   if (batch > c->max_batch) {
     ffcv::set_error("%s: batch %d exceeds ctx max_batch %d", fn, batch, c->max_batch);
     return FFCV_EINVAL;
@@ -461,6 +465,10 @@ int ffcv_jpeg_rrc_fused(ffcv_jpeg_ctx *c, void *stream, const uint8_t *base, con
   if (!c || !base || !table || !ids || !dp || !crops || !out || !status || batch < 0 || !p || p->out_h <= 0 ||
       p->out_w <= 0) {
     ffcv::set_error("ffcv_jpeg_rrc_fused: invalid arguments");
+    return FFCV_EINVAL;
+  }
+  if (batch > 65535) {  // as check_common
+    ffcv::set_error("ffcv_jpeg_rrc_fused: batch %d exceeds the 65535 images of one launch", batch);
     return FFCV_EINVAL;
   }
   if (batch > c->max_batch) {

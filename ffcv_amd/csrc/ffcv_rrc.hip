@@ -474,7 +474,7 @@ FFCV_DEV void rrc_band(const uint8_t *__restrict__ base, const ffcv_sample *__re
   if (s.mode != 1) return;
   const int oy0 = band * RRC_BAND, oy1 = min(p.out_h, oy0 + RRC_BAND);
   if (oy0 >= p.out_h) return;
-  const int ci = crops[4 * k], cj = crops[4 * k + 1], chh = crops[4 * k + 2], cww = crops[4 * k + 3];
+  const int ci = crops[4 * (size_t)k], cj = crops[4 * (size_t)k + 1], chh = crops[4 * (size_t)k + 2], cww = crops[4 * (size_t)k + 3];
   GlobalSrc src{base + s.offset + ((uint64_t)ci * s.width + cj) * 3, (uint64_t)s.width * 3};
   // the image's plan and linear taps from rrc_taps_kernel when the caller gave
   // a workspace (computed once per image, not in each of its band workgroups:
@@ -565,7 +565,7 @@ __global__ void __launch_bounds__(256) rrc_taps_kernel(const int32_t *__restrict
                                                        const uint8_t *__restrict__ flips, ffcv_rrc_params p,
                                                        ResizePlan *__restrict__ plans, uint2 *__restrict__ taps) {
   const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  const ResizePlan P = make_plan(crops[4 * k + 3], crops[4 * k + 2], p.out_w, p.out_h);
+  const ResizePlan P = make_plan(crops[4 * (size_t)k + 3], crops[4 * (size_t)k + 2], p.out_w, p.out_h);
   if (i == 0) plans[k] = P;
   if (area_walk_plan(P)) {  // column records of the area walk: {lo, w(lo), w(lo + 1), w(lo + 2)}, 0 past hi
     if (i >= p.out_w) return;
@@ -608,6 +608,14 @@ int ffcv_draw_batch(void *stream, const uint64_t *sample_ids, const ffcv_sample 
                            cutout_yx, flips, status);
 }
 
+// rrc_raw_kernel and rrc_taps_kernel take the image from blockIdx.y, and a grid
+// has at most 65,535 rows: a larger batch goes out in slices of that many
+// images, with the per-image pointers advanced (as flip and translate do).
+#define RRC_MAX_GRID_Y 65535
+static inline unsigned rrc_slice(int batch, int64_t k0) {
+  return (unsigned)(batch - k0 < RRC_MAX_GRID_Y ? batch - k0 : RRC_MAX_GRID_Y);
+}
+
 static uint64_t raw_plans_bytes(int batch) { return ((uint64_t)batch * sizeof(ResizePlan) + 255) & ~(uint64_t)255; }
 
 uint64_t ffcv_rrc_raw_workspace_bytes(int batch, int out_h, int out_w) {
@@ -637,23 +645,33 @@ int ffcv_rrc_raw_batch_ws(void *stream, const uint8_t *base, const ffcv_sample *
     }
     ResizePlan *wp = (ResizePlan *)workspace;
     uint2 *wt = (uint2 *)((uint8_t *)workspace + raw_plans_bytes(batch));
-    hipLaunchKernelGGL(rrc_taps_kernel, dim3((p->out_w + p->out_h + 255) / 256, batch), dim3(256), 0,
-                       ffcv::as_stream(stream), crops, flips, *p, wp, wt);
-    FFCV_LAUNCH_CHECK("rrc_taps_kernel");
+    for (int64_t k0 = 0; k0 < batch; k0 += RRC_MAX_GRID_Y) {
+      hipLaunchKernelGGL(rrc_taps_kernel, dim3((p->out_w + p->out_h + 255) / 256, rrc_slice(batch, k0)), dim3(256), 0,
+                         ffcv::as_stream(stream), crops + 4 * k0, flips ? flips + k0 : nullptr, *p, wp + k0,
+                         wt + (uint64_t)k0 * RAW_TAPS(*p));
+      FFCV_LAUNCH_CHECK("rrc_taps_kernel");
+    }
     plans = wp;
     taps = wt;
   }
   const bool fp16 = p->lut != nullptr;
   uint64_t dense = (uint64_t)p->out_h * p->out_w * 3 * (fp16 ? 2 : 1);
   uint64_t stride = p->out_stride ? p->out_stride : dense;
-  dim3 grid((p->out_h + RRC_BAND - 1) / RRC_BAND, batch);
-  if (fp16)
-    hipLaunchKernelGGL(rrc_raw_kernel<true>, grid, dim3(RRC_THREADS), 0, ffcv::as_stream(stream), base,
-                       samples, crops, cutout_yx, flips, *p, stride, out, plans, taps);
-  else
-    hipLaunchKernelGGL(rrc_raw_kernel<false>, grid, dim3(RRC_THREADS), 0, ffcv::as_stream(stream), base,
-                       samples, crops, cutout_yx, flips, *p, stride, out, plans, taps);
-  FFCV_LAUNCH_CHECK("rrc_raw_kernel");
+  for (int64_t k0 = 0; k0 < batch; k0 += RRC_MAX_GRID_Y) {
+    const dim3 grid((p->out_h + RRC_BAND - 1) / RRC_BAND, rrc_slice(batch, k0));
+    const int32_t *cut0 = cutout_yx ? cutout_yx + 2 * k0 : nullptr;
+    const uint8_t *flips0 = flips ? flips + k0 : nullptr;
+    const ResizePlan *plans0 = plans ? plans + k0 : nullptr;
+    const uint2 *taps0 = taps ? taps + (uint64_t)k0 * RAW_TAPS(*p) : nullptr;
+    void *out0 = (char *)out + stride * (uint64_t)k0;
+    if (fp16)
+      hipLaunchKernelGGL(rrc_raw_kernel<true>, grid, dim3(RRC_THREADS), 0, ffcv::as_stream(stream), base,
+                         samples + k0, crops + 4 * k0, cut0, flips0, *p, stride, out0, plans0, taps0);
+    else
+      hipLaunchKernelGGL(rrc_raw_kernel<false>, grid, dim3(RRC_THREADS), 0, ffcv::as_stream(stream), base,
+                         samples + k0, crops + 4 * k0, cut0, flips0, *p, stride, out0, plans0, taps0);
+    FFCV_LAUNCH_CHECK("rrc_raw_kernel");
+  }
   return FFCV_OK;
 }
 

@@ -64,7 +64,7 @@ FFCV_HD int draw_crop_transform(int k, uint64_t id, uint32_t H, uint32_t W, cons
   CropMT g;
   DevMT &m = g.m;
   mt_init(m, sample_seed(loader_seed, epoch, id, 8));
-  random_crop(g, H, W, scale, ratio, crops + 4 * k);
+  random_crop(g, H, W, scale, ratio, crops + 4 * (size_t)k);
   return m.err;
 }
 
@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(RRCI_THREADS)
   sx4_t *s_src = (sx4_t *)smem;
   uint8_t *s_tap = (uint8_t *)smem + src_cap;
   uint16_t *s_lut = (uint16_t *)(s_tap + (out_w + out_h) * RRCI_TAP_BYTES);
-  const int ci = crops[4 * k], cj = crops[4 * k + 1], chh = crops[4 * k + 2], cww = crops[4 * k + 3];
+  const int ci = crops[4 * (size_t)k], cj = crops[4 * (size_t)k + 1], chh = crops[4 * (size_t)k + 2], cww = crops[4 * (size_t)k + 3];
   char *o = (char *)out + stride * k;
   if (!crop_ok(ci, cj, chh, cww, H, W)) {  // (the same for the whole workgroup)
     const uint32_t dense = (uint32_t)out_h * out_w * 3 * (FP16 ? 2 : 1);
@@ -187,8 +187,8 @@ __global__ void __launch_bounds__(RRCI_THREADS)
   ep.out_h = out_h;
   ep.out_w = out_w;
   ep.cut_size = cut ? p.cutout_size : 0;
-  ep.cut_y = cut ? cut[2 * k] : 0;
-  ep.cut_x = cut ? cut[2 * k + 1] : 0;
+  ep.cut_y = cut ? cut[2 * (size_t)k] : 0;
+  ep.cut_x = cut ? cut[2 * (size_t)k + 1] : 0;
   ep.flip = flips ? flips[k] : 0;
   ep.cut_before_flip = p.cutout_fill[3];
   ep.fill[0] = p.cutout_fill[0];
@@ -339,7 +339,7 @@ __global__ void __launch_bounds__(RRCI_THREADS)
                            ffcv_sample *__restrict__ samples, int32_t *__restrict__ crops_out, uint64_t stride,
                            uint32_t dense, void *__restrict__ out, int32_t *__restrict__ status) {
   const int t = threadIdx.x, k = blockIdx.x;
-  const int ci = crops[4 * k], cj = crops[4 * k + 1], chh = crops[4 * k + 2], cww = crops[4 * k + 3];
+  const int ci = crops[4 * (size_t)k], cj = crops[4 * (size_t)k + 1], chh = crops[4 * (size_t)k + 2], cww = crops[4 * (size_t)k + 3];
   const bool ok = crop_ok(ci, cj, chh, cww, H, W);
   if (t == 0) {
     ffcv_sample s;
@@ -350,10 +350,10 @@ __global__ void __launch_bounds__(RRCI_THREADS)
     s.mode = ok ? 1u : 0u;
     s.reserved = 0;
     samples[k] = s;
-    crops_out[4 * k + 0] = ok ? ci : 0;
-    crops_out[4 * k + 1] = ok ? cj : 0;
-    crops_out[4 * k + 2] = ok ? chh : 1;
-    crops_out[4 * k + 3] = ok ? cww : 1;
+    crops_out[4 * (size_t)k + 0] = ok ? ci : 0;
+    crops_out[4 * (size_t)k + 1] = ok ? cj : 0;
+    crops_out[4 * (size_t)k + 2] = ok ? chh : 1;
+    crops_out[4 * (size_t)k + 3] = ok ? cww : 1;
     if (status) status[k] = ok ? FFCV_SAMPLE_OK : FFCV_SAMPLE_RANGE;
   }
   if (!ok) {
@@ -558,7 +558,7 @@ int ffcv_rrc_images_batch_host(const uint8_t *in, uint64_t in_stride, int batch,
   }
   ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
     for (int k = (int)next.fetch_add(1); k < batch; k = (int)next.fetch_add(1)) {
-      const int32_t *c = crops + 4 * k;
+      const int32_t *c = crops + 4 * (size_t)k;
       uint8_t *dst = out + (uint64_t)k * stride;
       if (!crop_ok(c[0], c[1], c[2], c[3], height, width)) {
         std::fill(dst, dst + dense, (uint8_t)0);

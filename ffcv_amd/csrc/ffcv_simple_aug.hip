@@ -45,13 +45,13 @@ __global__ void __launch_bounds__(AUG_THREADS)
   for (int i = 0; i < 3; i++) {
     const uint32_t st = i < n ? (prog >> (8 * i)) & 0xffu : 0u;
     if (st == FFCV_AUG_TRANSLATE) {
-      dy = tyx[2 * k] - p.padding;
-      dx = tyx[2 * k + 1] - p.padding;
+      dy = tyx[2 * (size_t)k] - p.padding;
+      dx = tyx[2 * (size_t)k + 1] - p.padding;
     }
     if (st == FFCV_AUG_FLIP) flip = flips[k] != 0;
     if (st == FFCV_AUG_CUTOUT) {
-      cy = cut[2 * k];
-      cx = cut[2 * k + 1];
+      cy = cut[2 * (size_t)k];
+      cx = cut[2 * (size_t)k + 1];
     }
   }
   const int cs = p.cutout_size;

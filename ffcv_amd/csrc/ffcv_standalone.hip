@@ -7,7 +7,7 @@ __global__ void __launch_bounds__(256) cutout_kernel(uint8_t *__restrict__ img, 
                                                      const int32_t *__restrict__ yx, int c, uint8_t f0,
                                                      uint8_t f1, uint8_t f2) {
   const int k = blockIdx.x;
-  const int y0 = yx[2 * k], x0 = yx[2 * k + 1];
+  const int y0 = yx[2 * (size_t)k], x0 = yx[2 * (size_t)k + 1];
   uint8_t *base = img + (uint64_t)k * H * W * 3;
   for (int i = threadIdx.x; i < c * c; i += 256) {
     int y = y0 + i / c, x = x0 + i % c;
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(256) translate_kernel(const uint8_t *__restric
                                                         uint8_t f0, uint8_t f1, uint8_t f2) {
   const int k = blockIdx.y;
   const uint64_t img = (uint64_t)H * W * 3;
-  const int64_t dy = (int64_t)yx[2 * k] - pad, dx = (int64_t)yx[2 * k + 1] - pad;
+  const int64_t dy = (int64_t)yx[2 * (size_t)k] - pad, dx = (int64_t)yx[2 * (size_t)k + 1] - pad;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < img; i += (uint64_t)gridDim.x * 256) {
     const uint64_t px = i / 3;
     const int b = (int)(i - px * 3);
@@ -129,9 +129,8 @@ int ffcv_lut_batch(void *stream, const uint8_t *in, uint64_t n, const void *lut,
     return FFCV_EINVAL;
   }
   if (n == 0) return FFCV_OK;
-  uint64_t groups = n / 12 + 1;
-  unsigned gx = (unsigned)((groups + 255) / 256);
-  if (gx > 8192) gx = 8192;
+  const uint64_t groups = n / 12 + 1, blocks = (groups + 255) / 256;
+  const unsigned gx = blocks > 8192 ? 8192u : (unsigned)blocks;
   hipStream_t s = ffcv::as_stream(stream);
   switch (elem_bytes) {
     case 1:

@@ -15,8 +15,8 @@ FFCV_DEV Epilogue make_epilogue(const ffcv_rrc_params &p, const int32_t *__restr
   ep.cut_size = ep.cut_y = ep.cut_x = 0;
   if (cut) {  // (one test: the origin is one 8-byte load)
     ep.cut_size = p.cutout_size;
-    ep.cut_y = cut[2 * k];
-    ep.cut_x = cut[2 * k + 1];
+    ep.cut_y = cut[2 * (size_t)k];
+    ep.cut_x = cut[2 * (size_t)k + 1];
   }
   ep.flip = flips ? flips[k] : 0;
   ep.cut_before_flip = p.cutout_fill[3];

@@ -1874,9 +1874,14 @@ class JpegDecoder:
     """Owns an ffcv_jpeg_ctx: launch scratch for up to max_batch images in
     one arena of arena_bytes (default: max_batch images of the maximum size)."""
 
+    MAX_LAUNCH = 65535     # images of one launch: the colour / resize kernels take the image from a grid row
+
     def __init__(self, max_batch, max_height, max_width, max_bytes, arena_bytes=0):
         self.handle = c_void_p()
         self.max_batch = int(max_batch)
+        if self.max_batch > self.MAX_LAUNCH:
+            raise FFCVError(f'JpegDecoder: max_batch {self.max_batch} exceeds the {self.MAX_LAUNCH} images of one '
+                            'launch')
         self.max_height, self.max_width = int(max_height), int(max_width)
         self.max_bytes = int(max_bytes)
         self.arena_bytes = int(arena_bytes)

@@ -220,7 +220,8 @@ int ffcv_draw_batch_host(const uint64_t *sample_ids, const uint32_t *heights,
  * INTER_AREA, fused with Cutout (cutout.py:44) and the NormalizeImage LUT
  * (normalize.py:65).  Samples with mode != raw are skipped.
  *   base  : device pointer to the .beton bytes (file offset 0)
- *   out   : device [B][out_h][out_w][3] uint8 (lut==NULL) or fp16 bits */
+ *   out   : device [B][out_h][out_w][3] uint8 (lut==NULL) or fp16 bits
+ * Any batch >= 0 (more than 65,535 samples go out as several launches). */
 int ffcv_rrc_raw_batch(void *stream, const uint8_t *base,
                        const ffcv_sample *samples, int batch,
                        const int32_t *crops, const int32_t *cutout_yx,
@@ -299,7 +300,8 @@ uint64_t ffcv_gather_rows_subwave(void);
  * TJFLAG_FASTDCT) (libffcv.cpp:104-106): ifast IDCT, fancy upsampling,
  * fixed-point YCbCr->RGB.  One context holds the scratch for up to
  * max_batch images of at most max_height x max_width pixels and max_bytes
- * compressed bytes each. */
+ * compressed bytes each.  A launch takes at most 65,535 images (and at most
+ * max_batch): a larger batch is FFCV_EINVAL before any launch. */
 typedef struct ffcv_jpeg_ctx ffcv_jpeg_ctx;
 int ffcv_jpeg_create(ffcv_jpeg_ctx **ctx, int max_batch, uint32_t max_height,
                      uint32_t max_width, uint64_t max_bytes);
