@@ -1,6 +1,8 @@
 // ffcv_augmix.hip -- AugMix: the draws (op ids 24 and 25), the
 // fused pixel pass for images up to 64 x 64, the streaming mix of the rounds
-// path beyond, and the host twins of the draws and of the mix.
+// path beyond, and the host twins of the draws and of the mix.  (The mix's
+// arithmetic is augmix_mix.h; the pixel pass for images up to 224 x 224 is
+// ffcv_augmix_large.hip.)
 //
 // A sample runs `width` (1..4) independent chains of 1..3 operations of s24,
 // each chain from the ORIGINAL image, and leaves as the float32 convex
@@ -40,21 +42,14 @@
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 #include "api_internal.h"
-#include "blur_common.h"
+#include "augmix_mix.h"
 #include "ra_slot.h"
 
 #define FFCV_AUGMIX_OP 24
 #define FFCV_AUGMIX_WEIGHT_OP 25
 #define AM_NBINS 10
-#define AM_MAX_WIDTH 4
-#define AM_MAX_DEPTH 3
 #define AM_LDS_BYTES (3 * RA_IMG_BYTES)  // the fused regime: 9 H W at most this
 #define AM_OWN (RA_IMG_BYTES / (4 * RA_THREADS))  // words of the image a thread owns
-
-// ------------------------------------------------------------- the mix --
-FFCV_HD float augmix_first(float w, float x) { return blur_mul(w, x); }
-FFCV_HD float augmix_add(float acc, float w, float y) { return blur_add(acc, blur_mul(w, y)); }
-FFCV_HD uint32_t augmix_byte(float acc) { return (uint32_t)sat_u8i(ffcv_f2i_rn(acc)); }  // half to even, capped
 
 // ----------------------------------------------------------- the draws --
 // Stream 24 of one sample.  Returns 1 when the MT19937 stream ran out.
@@ -391,34 +386,6 @@ struct AmMixIn {
   const uint8_t *img[1 + AM_MAX_WIDTH];  // the original, then the chains' results
 };
 
-// The 16 bytes from address a on, of which bytes [jlo, jhi) are wanted, from
-// the one or two ALIGNED 16-byte chunks that hold a wanted byte (a chunk that
-// holds none is not touched: it may lie in a page that is not ours).
-FFCV_DEV lds_x4_t am_load16(uint64_t a, int jlo, int jhi) {
-  const uint64_t a0 = a & ~(uint64_t)15;
-  const glb_x4_t *p = (const glb_x4_t *)(uintptr_t)a0;
-  lds_x4_t lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-  if (a + (uint64_t)jlo < a0 + 16u) lo = p[0];
-  if (a + (uint64_t)jhi > a0 + 16u) hi = p[1];
-  const uint32_t sh = (uint32_t)(a & 15), d = sh >> 2, r = sh & 3u;
-  uint32_t w[9] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w, 0u};
-  // by whole dwords (two selects), then by bytes
-  if (d & 2u) {
-#pragma unroll
-    for (int i = 0; i < 7; i++) w[i] = w[i + 2];
-  }
-  if (d & 1u) {
-#pragma unroll
-    for (int i = 0; i < 5; i++) w[i] = w[i + 1];
-  }
-  lds_x4_t v;
-  v.x = __builtin_amdgcn_alignbyte(w[1], w[0], r);
-  v.y = __builtin_amdgcn_alignbyte(w[2], w[1], r);
-  v.z = __builtin_amdgcn_alignbyte(w[3], w[2], r);
-  v.w = __builtin_amdgcn_alignbyte(w[4], w[3], r);
-  return v;
-}
-
 // One thread per aligned 16-byte chunk of `out` that holds a byte of image k.
 __global__ void __launch_bounds__(256)
     augmix_mix_kernel(AmMixIn in, int width, const float *__restrict__ weights, uint8_t *__restrict__ out, uint32_t B,
@@ -436,31 +403,10 @@ __global__ void __launch_bounds__(256)
     if (i > width) break;
     const float w = weights[(uint64_t)i * B + k];
     const lds_x4_t v = am_load16((uint64_t)(uintptr_t)in.img[i] + (uint64_t)k * img + (uint64_t)b0, jlo, jhi);
-    const uint32_t word[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      const float y = (float)((word[e >> 2] >> (8 * (e & 3))) & 0xffu);
-      acc[e] = i == 0 ? augmix_first(w, y) : augmix_add(acc[e], w, y);
-    }
+    am_mix16(acc, i == 0, w, v);
   }
   uint8_t *gb = (uint8_t *)(uintptr_t)((da & ~(uint64_t)15) + 16u * (uint64_t)c);
-  if (jlo == 0 && jhi == 16) {
-    lds_x4_t o;
-    uint32_t word[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++)
-      word[e] = augmix_byte(acc[4 * e]) | augmix_byte(acc[4 * e + 1]) << 8 | augmix_byte(acc[4 * e + 2]) << 16 |
-                augmix_byte(acc[4 * e + 3]) << 24;
-    o.x = word[0];
-    o.y = word[1];
-    o.z = word[2];
-    o.w = word[3];
-    *(glb_x4_t *)gb = o;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 16; e++)
-      if (e >= jlo && e < jhi) gb[e] = (uint8_t)augmix_byte(acc[e]);
-  }
+  am_store16(gb, acc, jlo, jhi);
 }
 
 namespace {

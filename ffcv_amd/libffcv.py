@@ -276,6 +276,10 @@ _SIGS = {
     'ffcv_augmix_lds_bytes': (c_uint64, []),
     'ffcv_augmix_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p] +
                           [c_void_p] * 11),
+    'ffcv_augmix_large_slab_bytes': (c_uint64, [c_int, c_int, c_int]),
+    'ffcv_augmix_large_workspace_bytes': (c_uint64, [c_int, c_int, c_int]),
+    'ffcv_augmix_large_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p] +
+                                [c_void_p] * 11 + [c_void_p, c_uint64]),
     'ffcv_augmix_mix_batch': (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int]),
     'ffcv_augmix_mix_batch_host': (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
 }
@@ -1324,22 +1328,61 @@ def augmix_lds_bytes():
     return int(lib().ffcv_augmix_lds_bytes())
 
 
-def augmix_batch(src, dst, width, mode, fill, d, stream=None):
-    """Every chain of every sample of a dense device uint8 (B, H, W, 3) batch
-    and the mix in ONE launch, into ``dst`` (ffcv_augmix_batch; images up to
-    augmix_lds_bytes()); d: the device arrays of augmix_draw_batch."""
-    B, H, W = _u8_batch_dims(src, 'augmix_batch')
+def _augmix_pixels(entry, src, dst, width, mode, fill, d, stream, *tail):
+    who = entry[len('ffcv_'):]
+    B, H, W = _u8_batch_dims(src, who)
     if tuple(dst.shape) != tuple(src.shape) or not dst.is_contiguous():
-        raise TypeError(f'augmix_batch: a contiguous dst of shape {tuple(src.shape)} is required')
+        raise TypeError(f'{who}: a contiguous dst of shape {tuple(src.shape)} is required')
     arrays = augmix_arrays(width)
     for name, dt, shape in arrays:
         a = d[name]
         if tuple(a.shape) != shape(B) or a.element_size() != np.dtype(dt).itemsize or not a.is_contiguous():
-            raise TypeError(f'augmix_batch: {name} must be a contiguous {np.dtype(dt).name} {shape(B)}')
+            raise TypeError(f'{who}: {name} must be a contiguous {np.dtype(dt).name} {shape(B)}')
     f = fill_u8(fill)
-    _check(lib().ffcv_augmix_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(width), int(mode), _p(f),
-                                   *[_p(d[name]) for name, _, _ in arrays]), 'ffcv_augmix_batch')
+    _check(getattr(lib(), entry)(_stream(stream), _p(src), _p(dst), B, H, W, int(width), int(mode), _p(f),
+                                 *[_p(d[name]) for name, _, _ in arrays], *tail), entry)
     return dst
+
+
+def augmix_batch(src, dst, width, mode, fill, d, stream=None):
+    """Every chain of every sample of a dense device uint8 (B, H, W, 3) batch
+    and the mix in ONE launch, into ``dst`` (ffcv_augmix_batch; images up to
+    augmix_lds_bytes()); d: the device arrays of augmix_draw_batch."""
+    return _augmix_pixels('ffcv_augmix_batch', src, dst, width, mode, fill, d, stream)
+
+
+def augmix_large_fits(height, width):
+    """Does augmix_large_batch take images of this shape?  The shapes of
+    randaugment_large_fits: the two kernels share the slot code and its bounds."""
+    return randaugment_large_fits(height, width)
+
+
+def augmix_large_slab_bytes(height, width, mixture_width):
+    """The scratch of one workgroup of augmix_large_batch: the results of all
+    chains but the last, as bytes."""
+    return int(lib().ffcv_augmix_large_slab_bytes(int(height), int(width), int(mixture_width)))
+
+
+def augmix_large_workspace_bytes(height, width, mixture_width):
+    """The workspace of augmix_large_batch with one slab per compute unit of
+    the current device, whatever the batch."""
+    n = int(lib().ffcv_augmix_large_workspace_bytes(int(height), int(width), int(mixture_width)))
+    if not n:
+        raise FFCVError('ffcv_augmix_large_workspace_bytes failed: ' +
+                        lib().ffcv_last_error().decode(errors='replace'))
+    return n
+
+
+def augmix_large_batch(src, dst, width, mode, fill, d, workspace, stream=None):
+    """augmix_batch for images beyond its regime, up to 224 x 224
+    (ffcv_augmix_large_batch: ONE launch of min(B, slabs) persistent
+    workgroups, one image buffer in LDS; the shapes of augmix_large_fits).
+    workspace: a contiguous device uint8 tensor that holds at least one
+    augmix_large_slab_bytes(); its size decides the number of workgroups."""
+    if workspace.element_size() != 1 or not workspace.is_contiguous():
+        raise TypeError('augmix_large_batch: a contiguous uint8 workspace is required')
+    return _augmix_pixels('ffcv_augmix_large_batch', src, dst, width, mode, fill, d, stream, _p(workspace),
+                          int(workspace.numel()))
 
 
 def _augmix_mix_args(orig, results, weights, out, who):

@@ -386,9 +386,13 @@ class AugMix(_U8ImageOp):
 
     On device tensors it is the draw's launches and, for images up to 64 x 64
     (``libffcv.augmix_lds_bytes()``), ONE pixel launch (ffcv_augmix_batch);
-    beyond, per chain a copy and the rounds of RandAugment, then one streaming
-    launch for the mix (ffcv_augmix_mix_batch).  On host arrays it is the host
-    twins of the rounds and of the mix.
+    from ``libffcv.randaugment_large_min_bytes()`` bytes per image up to
+    224 x 224 (``libffcv.augmix_large_fits``) ONE launch too, of persistent
+    workgroups with a single image buffer in LDS, the chains' results passing
+    through a workspace of one slab per compute unit (ffcv_augmix_large_batch);
+    otherwise, per chain a copy and the rounds of RandAugment, then one
+    streaming launch for the mix (ffcv_augmix_mix_batch).  On host arrays it
+    is the host twins of the rounds and of the mix.
 
     Parameters
     ----------
@@ -463,6 +467,7 @@ class AugMix(_U8ImageOp):
         draw = (self.severity, width, self.chain_depth, self.alpha, self.all_ops)
         rounds = self.chain_depth if self.chain_depth > 0 else L.AUGMIX_MAX_DEPTH
         key = ('aug_mix', id(self))
+        ws_bytes = {}              # (H, W) -> the workspace of the launch for images beyond 64 x 64
 
         def chain_buffers(i, result, spare):
             """Where chain i's copy of the input goes, then where each round
@@ -482,6 +487,15 @@ class AugMix(_U8ImageOp):
                                 H, W, d, None, ctx.stream)
             if 9 * H * W <= L.augmix_lds_bytes():
                 L.augmix_batch(images, out, width, mode, fill, d, ctx.stream)
+                return
+            if 3 * H * W >= L.randaugment_large_min_bytes() and L.augmix_large_fits(H, W):
+                # one slab per compute unit, or per image of a smaller batch
+                n = ws_bytes.get((H, W))
+                if n is None:
+                    n = ws_bytes[(H, W)] = L.augmix_large_workspace_bytes(H, W, width)
+                n = min(n, ctx.batch_size * L.augmix_large_slab_bytes(H, W, width) + 16)
+                L.augmix_large_batch(images, out, width, mode, fill, d,
+                                     ctx.device_buffer(key + ('large_ws',), n, ch.uint8)[:n], ctx.stream)
                 return
             # per chain a copy of the input and RandAugment's rounds, then the streaming mix
             cj_ws = tone_ws = None

@@ -1341,6 +1341,38 @@ int ffcv_augmix_mix_batch_host(const uint8_t *orig, const uint8_t *r0,
                                const uint8_t *r3, int mixture_width,
                                const float *weights, uint8_t *out, int batch,
                                int height, int width, int nthreads);
+/* ffcv_augmix_batch for images beyond its regime, up to 224 x 224 (the shapes
+ * of ffcv_randaugment_large_fits, smaller ones included): ONE launch of
+ * persistent workgroups, min(batch, slabs) of them, each taking every
+ * slabs-th image.  A chain runs in the one image buffer in LDS; the results of
+ * all chains but the last go as bytes to the workgroup's slab of the
+ * workspace, and the mix reads them back in the same launch.
+ *   workspace       : device memory of workspace_bytes bytes, at any
+ *                     alignment, read and written; the number of slabs is the
+ *                     number of whole ffcv_augmix_large_slab_bytes() that fit
+ *                     in it from its first 16-byte boundary on
+ * ffcv_augmix_large_slab_bytes(height, width, mixture_width): a slab, which is
+ * max(mixture_width - 1, 1) results of 16 * ((3 height width + 30) / 16) bytes
+ * (an image in the 16-byte phase of its place in dst); 0 for arguments the
+ * entry refuses.  ffcv_augmix_large_workspace_bytes(...): one slab per compute
+ * unit of the current device and 16 bytes for the alignment; 0 when the
+ * arguments are refused or the device cannot be asked (ffcv_last_error).
+ * FFCV_EINVAL, before any launch, as ffcv_augmix_batch, for a shape
+ * ffcv_randaugment_large_fits refuses, or a null workspace or one smaller than
+ * one slab (batch > 0). */
+uint64_t ffcv_augmix_large_slab_bytes(int height, int width, int mixture_width);
+uint64_t ffcv_augmix_large_workspace_bytes(int height, int width,
+                                           int mixture_width);
+int ffcv_augmix_large_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                            int batch, int height, int width,
+                            int mixture_width, int mode, const uint8_t *fill,
+                            const uint8_t *op, const uint8_t *cj_apply,
+                            const double *cj_ratio, const uint8_t *tone_apply,
+                            const uint8_t *tone_bits, const uint8_t *aff_apply,
+                            const int64_t *aff_coef, const uint8_t *sharp_apply,
+                            const float *sharp_factor, const uint8_t *depth,
+                            const float *weights, void *workspace,
+                            uint64_t workspace_bytes);
 
 /* ------------------------------------------------- random erasing ------ */
 /* RandomErasing.  The draws of sample k, from its own MT19937

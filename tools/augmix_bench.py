@@ -1,15 +1,19 @@
 """AugMix (DESIGN s28): what the fused path (the draw launches and ONE pixel
-launch that keeps the original in LDS, runs the chains there and mixes in
-registers) costs next to the rounds path (the draw launches, per chain a copy
+launch: up to 64 x 64 the original stays in LDS, the chains run there and the
+mix is in registers; beyond, persistent workgroups with one image buffer in
+LDS pass the chains' results through a slab of memory each) costs next to the
+rounds path (the draw launches, per chain a copy
 and three rounds of the five pixel launches of TrivialAugmentWide, then the
 streaming mix) and next to a device-to-device copy.
 
     python tools/augmix_bench.py [--reps 40] [--rounds 3] [--warmup 5] [--ring-mb 640] [--width 3]
 
-Shapes: 512 x 32 x 32 and 256 x 64 x 64 (the edge of the fused regime),
-uniformly random pixels, severity 3, random depth, alpha 1, nearest.
+Shapes: 512 x 32 x 32 and 256 x 64 x 64 (the edge of ffcv_augmix_batch), and
+256 x 128 x 128 and 256 x 224 x 224 (ffcv_augmix_large_batch, a workspace of
+ffcv_augmix_large_workspace_bytes), uniformly random pixels, severity 3, random
+depth, alpha 1, nearest.
 
-  fused   ffcv_augmix_draw_batch, ffcv_augmix_batch
+  fused   ffcv_augmix_draw_batch, ffcv_augmix_batch or ffcv_augmix_large_batch
   rounds  ffcv_augmix_draw_batch, then the operation's launches beyond the
           fused regime (the baseline: existing kernels and ffcv_augmix_mix_batch)
   d2d     one device-to-device copy of the same bytes
@@ -31,7 +35,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CASES = ((512, 32, 32), (256, 64, 64))
+CASES = ((512, 32, 32), (256, 64, 64), (256, 128, 128), (256, 224, 224))
 CJ_STEPS, SOLARIZE_STEPS, TONE_STEPS = (1, 3, 2), (5,), (1, 2, 3)
 SEVERITY, DEPTH, ALPHA, SEED = 3, -1, 1.0, 3
 
@@ -56,7 +60,8 @@ def main():
     variants = ('fused', 'rounds', 'd2d')
     mode, fill = L.AFFINE_NEAREST, (0, 0, 0)
     for B, H, W in CASES:
-        assert 9 * H * W <= L.augmix_lds_bytes()
+        large = 9 * H * W > L.augmix_lds_bytes()
+        assert not large or (3 * H * W >= L.randaugment_large_min_bytes() and L.augmix_large_fits(H, W))
         nbytes = B * H * W * 3
         nring = max(2, -(-args.ring_mb * (1 << 20) // nbytes))
         rings = {name: [ch.empty((B, H, W, 3), dtype=ch.uint8, device=dev) for _ in range(nring)]
@@ -69,6 +74,10 @@ def main():
              for name, dt, shape in L.augmix_arrays(width)}
         results = [ch.empty((B, H, W, 3), dtype=ch.uint8, device=dev) for _ in range(width)]
         spare = ch.empty((B, H, W, 3), dtype=ch.uint8, device=dev)
+        # the work buffers of the operation's device code, as it allocates them
+        cj_ws = ch.empty(B, dtype=ch.int64, device=dev) if H * W * 3 > L.color_jitter_lds_bytes() else None
+        tone_ws = ch.empty(768 * B, dtype=ch.int32, device=dev) if H * W * 3 > L.tone_lds_bytes() else None
+        large_ws = ch.empty(L.augmix_large_workspace_bytes(H, W, width) if large else 0, dtype=ch.uint8, device=dev)
 
         def draw():
             L.augmix_draw_batch(ids, SEED, 0, SEVERITY, width, DEPTH, ALPHA, True, table, H, W, d)
@@ -81,9 +90,9 @@ def main():
                 for r in range(3):
                     cur, nxt = bufs[r], bufs[r + 1]
                     a = L.randaugment_slot(d, 3 * i + r)
-                    L.color_jitter_batch(cur, CJ_STEPS, a['cj_apply'][:3], a['cj_ratio'][:3])
+                    L.color_jitter_batch(cur, CJ_STEPS, a['cj_apply'][:3], a['cj_ratio'][:3], cj_ws)
                     L.color_jitter_batch(cur, SOLARIZE_STEPS, a['cj_apply'][3:], a['cj_ratio'][3:])
-                    L.tone_batch_bits(cur, TONE_STEPS, a['tone_apply'], a['tone_bits'])
+                    L.tone_batch_bits(cur, TONE_STEPS, a['tone_apply'], a['tone_bits'], tone_ws)
                     L.affine_batch(cur, nxt, mode, fill, a['aff_apply'], a['aff_coef'])
                     L.sharpness_batch(cur, nxt, a['sharp_apply'], a['sharp_factor'])
             L.augmix_mix_batch(x, results, d['weights'], dst)
@@ -94,15 +103,20 @@ def main():
                 dst.copy_(src)
             elif name == 'fused':
                 draw()
-                L.augmix_batch(src, dst, width, mode, fill, d)
+                if large:
+                    L.augmix_large_batch(src, dst, width, mode, fill, d, large_ws)
+                else:
+                    L.augmix_batch(src, dst, width, mode, fill, d)
             else:
                 run_rounds(src, dst)
         res = {'unit': 'us', 'batch': B, 'shape': f'{H}x{W}', 'width': width, 'bytes': 2 * nbytes, 'ring': nring,
+               'entry': 'ffcv_augmix_large_batch' if large else 'ffcv_augmix_batch',
                'config': f'{args.reps} launches x {args.rounds} rounds'}
         run(0, 'fused')
         fused_out = rings['dst'][0].clone()
         run(0, 'rounds')
         res['fused_equals_rounds'] = bool(ch.equal(fused_out, rings['dst'][0]))
+        assert res['fused_equals_rounds'], res
         res['changed'] = int((fused_out != rings['src'][0]).flatten(1).any(dim=1).sum())
         for name in variants:
             for i in range(args.warmup):
