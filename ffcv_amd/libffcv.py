@@ -161,6 +161,11 @@ _SIGS = {
     'ffcv_rrc_images_lds_bytes': (c_uint64, []),
     'ffcv_rrc_images_batch_host': (c_int, [c_void_p, c_uint64, c_int, c_int, c_int, c_void_p, c_int, c_int,
                                            c_void_p, c_uint64, c_void_p, c_int]),
+    'ffcv_resample_images_batch': (c_int, [c_void_p, c_uint64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                           c_void_p, c_uint64, c_void_p, c_void_p]),
+    'ffcv_resample_images_batch_host': (c_int, [c_void_p, c_uint64, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                                c_int, c_void_p, c_uint64, c_void_p, c_int]),
+    'ffcv_resample_fits': (c_int, [c_int, c_int, c_int, c_int, c_int]),
     'ffcv_simple_aug_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
     'ffcv_color_jitter_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_double,
@@ -767,6 +772,44 @@ def rrc_images_batch_host(inp: np.ndarray, crops, out: np.ndarray, status=None, 
     _check(lib().ffcv_rrc_images_batch_host(_p(inp), H * W * 3, B, H, W, _p(crops), int(out.shape[1]),
                                             int(out.shape[2]), _p(out), int(out[0].nbytes) if B else 0, _p(status),
                                             int(max(1, nthreads))), 'ffcv_rrc_images_batch_host')
+    return out[:B]
+
+
+RESAMPLE_MODES = {'bilinear': 1, 'bicubic': 2}   # FFCV_RESAMPLE_BILINEAR, FFCV_RESAMPLE_BICUBIC
+
+
+def resample_fits(height, width, out_h, out_w, mode):
+    """Whether resample_images_batch (and its host twin) serves this shape."""
+    return bool(lib().ffcv_resample_fits(int(height), int(width), int(out_h), int(out_w), RESAMPLE_MODES[mode]))
+
+
+def resample_images_batch(inp, in_stride, batch, height, width, crops, mode, out_h, out_w, out, out_stride=0,
+                          status=None, stream=None):
+    """Pillow's crop(window).resize((out_w, out_h), BILINEAR | BICUBIC) of a
+    dense device uint8 batch of height x width x 3 images, image k at
+    ``inp + k * in_stride``, into uint8 images ``out_stride`` bytes apart
+    (ffcv_resample_images_batch): ONE launch."""
+    _check(lib().ffcv_resample_images_batch(
+        _p(inp), int(in_stride), int(batch), int(height), int(width), _p(crops), RESAMPLE_MODES[mode], int(out_h),
+        int(out_w), _p(out), int(out_stride), _p(status), _stream(stream)), 'ffcv_resample_images_batch')
+
+
+def resample_images_batch_host(inp: np.ndarray, crops, mode, out: np.ndarray, status=None, nthreads=1):
+    """The same on C-contiguous numpy uint8 arrays: inp (B, H, W, 3), crops
+    int32 (B, 4), out (B, out_h, out_w, 3); an invalid crop gives a zero image
+    and status 8 (status: int32 (B,) or None)."""
+    if not (isinstance(inp, np.ndarray) and isinstance(out, np.ndarray) and inp.dtype == np.uint8 and
+            out.dtype == np.uint8 and inp.ndim == 4 and out.ndim == 4 and inp.shape[3] == 3 and out.shape[3] == 3
+            and inp.flags.c_contiguous and out.flags.c_contiguous and out.shape[0] >= inp.shape[0]):
+        raise TypeError('resample_images_batch_host: C-contiguous uint8 (B, H, W, 3) arrays are required')
+    crops = np.ascontiguousarray(crops, np.int32)
+    B, H, W = (int(x) for x in inp.shape[:3])
+    if crops.shape != (B, 4):
+        raise TypeError(f'resample_images_batch_host: crops must be int32 ({B}, 4), got {crops.shape}')
+    _check(lib().ffcv_resample_images_batch_host(_p(inp), H * W * 3, B, H, W, _p(crops), RESAMPLE_MODES[mode],
+                                                 int(out.shape[1]), int(out.shape[2]), _p(out),
+                                                 int(out[0].nbytes) if B else 0, _p(status), int(max(1, nthreads))),
+           'ffcv_resample_images_batch_host')
     return out[:B]
 
 

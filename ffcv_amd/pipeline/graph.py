@@ -244,6 +244,8 @@ class Graph:
                 continue
             if not all(getattr(o, 'device_aware', False) for o in chain[:i]):
                 continue
+            if op.interpolation != 'area':   # the resample launch applies no epilogue
+                continue
             cutout, flip, cut_before_flip, norm = self._scan_epilogue(chain[i + 1:])
             op.fuse(cutout=cutout, flip=flip, cutout_before_flip=cut_before_flip, normalize=norm)
 

@@ -17,6 +17,14 @@ decoder's band kernel).  The graph lowering absorbs a following Cutout /
 RandomHorizontalFlip / NormalizeImage(float16) into that launch
 (``_lower_rrc_transform``).  On host arrays it is the host draws plus
 ``resize()`` per image over the Loader's threads.
+
+``interpolation='bilinear'`` / ``'bicubic'`` resize as torchvision's
+``resized_crop`` does on PIL images (the timm / DeiT / ConvNeXt recipes):
+Pillow's antialiased ``img.crop(window).resize(size, BILINEAR | BICUBIC)``,
+byte for byte.  The draws are the same; the resize is ONE
+launch of ffcv_resample_images_batch on the device and its host twin on host
+arrays.  These modes absorb no epilogue: the output is uint8 and a following
+Cutout / flip / NormalizeImage runs as its own launch.
 """
 import numbers
 from dataclasses import replace
@@ -45,14 +53,24 @@ class RandomResizedCrop(FusesEpilogue, Operation):
         Lower and upper bounds for random aspect ratio of the crop.
     size : int
         Side length of the output.
+    interpolation : str
+        'area' (cv::resize INTER_AREA, the reference's), 'bilinear' or
+        'bicubic' (Pillow's antialiased resize of the cropped window).
     """
     device_aware = True
     per_sample = True
 
-    def __init__(self, scale: Tuple[float, float], ratio: Tuple[float, float], size: int):
+    INTERPOLATIONS = ('area', 'bilinear', 'bicubic')
+
+    def __init__(self, scale: Tuple[float, float], ratio: Tuple[float, float], size: int,
+                 interpolation: str = 'area'):
         super().__init__()
         if isinstance(size, bool) or not isinstance(size, numbers.Integral) or size <= 0:
             raise ValueError(f'RandomResizedCrop: size must be an int > 0, got {size!r}')
+        if not isinstance(interpolation, str) or interpolation not in self.INTERPOLATIONS:
+            raise ValueError(f'RandomResizedCrop: interpolation must be one of {self.INTERPOLATIONS}, '
+                             f'got {interpolation!r}')
+        self.interpolation = interpolation
         self.scale = scale
         self.ratio = ratio
         self.size = int(size)
@@ -72,7 +90,45 @@ class RandomResizedCrop(FusesEpilogue, Operation):
                              f'{self.ratio!r}')
         return scale, ratio
 
+    def _generate_resample(self) -> Callable:
+        """'bilinear' / 'bicubic': the draws, then one resample launch (or the host twin)."""
+        from .. import libffcv as L
+        scale, ratio = self._ranges()
+        size, mode = self.size, self.interpolation
+
+        def random_resized_crop(images, storage, indices):
+            dst, crops = storage
+            ctx = runtime.current()
+            if isinstance(images, ch.Tensor) and images.device.type == 'cuda':
+                if not images.is_contiguous():
+                    raise TypeError('RandomResizedCrop: a contiguous (B, H, W, 3) batch is required')
+                B, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+                L.crop_draw_batch(ctx.batch_ids, H, W, scale, ratio, ctx.loader_seed, ctx.epoch, crops, None,
+                                  ctx.stream)
+                out = dst[:B]
+                L.resample_images_batch(images, H * W * 3, B, H, W, crops, mode, size, size, out, 0, None,
+                                        ctx.stream)
+                return out
+            seed, epoch = (ctx.loader_seed, ctx.epoch) if ctx else (0, 0)
+            src = images.numpy() if isinstance(images, ch.Tensor) else images
+            src = np.ascontiguousarray(src)
+            B = len(indices)
+            out = dst[:B]
+            out_np = out.numpy() if isinstance(out, ch.Tensor) else out
+            from ..pipeline.compiler import Compiler
+            cr = L.crop_draw_batch_host(np.asarray(indices, np.uint64), src.shape[1], src.shape[2], scale, ratio,
+                                        seed, epoch)
+            crops_np = crops.numpy() if isinstance(crops, ch.Tensor) else crops
+            crops_np[:B] = cr
+            L.resample_images_batch_host(src[:B], cr, mode, out_np, None, nthreads=max(1, int(Compiler.num_threads)))
+            return out
+        random_resized_crop.is_parallel = True
+        random_resized_crop.with_indices = True
+        return random_resized_crop
+
     def generate_code(self) -> Callable:
+        if self.interpolation != 'area':
+            return self._generate_resample()
         from .. import libffcv as L
         scale, ratio = self._ranges()
         size = self.size
@@ -132,6 +188,13 @@ class RandomResizedCrop(FusesEpilogue, Operation):
     def declare_state_and_memory(self, previous_state: State) -> Tuple[State, Optional[AllocationQuery]]:
         dt, _ = check_u8_images('RandomResizedCrop', previous_state)
         self._ranges()
+        if self.interpolation != 'area':
+            from .. import libffcv as L
+            H, W = int(previous_state.shape[0]), int(previous_state.shape[1])
+            if not L.resample_fits(H, W, self.size, self.size, self.interpolation):
+                raise ValueError(f"RandomResizedCrop: interpolation={self.interpolation!r} from {H}x{W} to "
+                                 f'{self.size}x{self.size} needs more than the 64 KiB of LDS a workgroup may use '
+                                 '(ffcv_resample_fits); images and outputs of up to 256x256 always fit')
         out_shape = (self.size, self.size, 3)
         on_dev = previous_state.device.type == 'cuda'
         if on_dev:

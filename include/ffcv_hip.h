@@ -518,6 +518,51 @@ int ffcv_rrc_images_batch_host(const uint8_t *in, uint64_t in_stride,
                                uint8_t *out, uint64_t out_stride,
                                int32_t *status, int nthreads);
 
+/* ------------------------------- Pillow-exact crop + resample --------- */
+enum {
+  FFCV_RESAMPLE_BILINEAR = 1, /* Pillow's BILINEAR: support 1 */
+  FFCV_RESAMPLE_BICUBIC = 2   /* Pillow's BICUBIC: support 2, a = -0.5 */
+};
+/* Image k of `out` = PIL's in_k.crop(window).resize((out_w, out_h), mode)
+ * with crops[k] = (i, j, h, w), byte for byte: the antialiased separable
+ * resampler of Pillow's 8-bit images (a horizontal pass to a uint8
+ * intermediate, then a vertical pass; float64 weights normalised per output
+ * sample and rounded to 22-bit fixed point; taps clamp at the WINDOW's
+ * edges).  uint8 HWC in and out.
+ *   in    : device uint8, image k at in + k * in_stride, height x width x 3
+ *           with dense rows, at ANY byte alignment; read with aligned 16-byte
+ *           loads under the rule of ffcv_rrc_images_batch.
+ *   crops : device int32[B][4], validated on the device as in
+ *           ffcv_rrc_images_batch: an invalid window's image is not read, its
+ *           output is zero-filled and status[k] = FFCV_SAMPLE_RANGE.
+ *   out   : device uint8, image k at out + k * out_stride (0 = dense), at ANY
+ *           byte alignment, must not overlap `in`; only each image's own bytes
+ *           are written.  status: device or NULL.
+ * ONE launch, no workspace: a workgroup per band of output rows of an image
+ * builds its coefficient records in LDS and rolls both passes over the
+ * window's rows.  The shapes served are those of ffcv_resample_fits (1 / 0):
+ * every height, width <= 256 with every square output of 1 .. 256 in both
+ * modes, and beyond that whatever fits a workgroup's 64 KiB of LDS.
+ * batch == 0 returns FFCV_OK without a launch.  FFCV_EINVAL, before any
+ * launch, for a null in / crops / out, batch < 0, sizes <= 0 or > 65535,
+ * another mode, in_stride < height * width * 3, an out_stride smaller than an
+ * image, overlapping in and out, or a shape ffcv_resample_fits refuses. */
+int ffcv_resample_images_batch(const uint8_t *in, uint64_t in_stride,
+                               int batch, int height, int width,
+                               const int32_t *crops, int mode, int out_h,
+                               int out_w, uint8_t *out, uint64_t out_stride,
+                               int32_t *status, void *stream);
+/* The same on host memory over nthreads threads, from the same coefficient
+ * function (host and device coefficients are equal as bits); the same guards
+ * and the same shapes. */
+int ffcv_resample_images_batch_host(const uint8_t *in, uint64_t in_stride,
+                                    int batch, int height, int width,
+                                    const int32_t *crops, int mode, int out_h,
+                                    int out_w, uint8_t *out,
+                                    uint64_t out_stride, int32_t *status,
+                                    int nthreads);
+int ffcv_resample_fits(int height, int width, int out_h, int out_w, int mode);
+
 /* ------------------------------- fused small-image augmentation ------- */
 /* Geometric steps of ffcv_simple_aug_batch's program. */
 enum {
