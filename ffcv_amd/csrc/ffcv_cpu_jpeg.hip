@@ -27,6 +27,7 @@
 #include <string>
 
 #include "api_internal.h"
+#include "resample_passes.h"
 
 namespace {
 
@@ -1021,13 +1022,15 @@ int imdecode(unsigned char *input_buffer, uint64_t input_size, uint32_t source_h
 // status[k] = 0, or -1 when its decode failed (ffcv_last_error() holds the
 // last message).  Samples are handed out one at a time from an atomic
 // counter (their sizes differ).
-int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, const uint32_t *heights,
-                          const uint32_t *widths, const uint32_t *modes, int batch, const int32_t *crops,
-                          int out_h, int out_w, uint8_t *out, uint64_t out_stride, int nthreads,
-                          int32_t *status) {
+// (rmode: 0, or the FFCV_RESAMPLE_* filter that takes resize()'s place for
+// samples of at most max_h x max_w: ffcv_cpu_decode_resample_batch)
+static int cpu_decode_batch(const char *who, const uint8_t *const *data, const uint64_t *sizes,
+                            const uint32_t *heights, const uint32_t *widths, const uint32_t *modes, int batch,
+                            const int32_t *crops, int rmode, int out_h, int out_w, uint8_t *out, uint64_t out_stride,
+                            int max_h, int max_w, int nthreads, int32_t *status) {
   if (batch < 0 || (batch > 0 && (!data || !sizes || !heights || !widths || !modes || !out || !status)) ||
       (crops && (out_h <= 0 || out_w <= 0))) {
-    ffcv::set_error("ffcv_cpu_decode_batch: invalid arguments");
+    ffcv::set_error("%s: invalid arguments", who);
     return FFCV_EINVAL;
   }
   // the first failing sample's message: set_error is thread-local, so a
@@ -1045,10 +1048,22 @@ int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, con
   };
   ffcv::host_threads(nthreads, batch, [&](std::atomic<uint64_t> &next, int, int) {
     std::vector<uint8_t> img;
+    ResampleHostScratch rscr;
     for (int k = (int)next.fetch_add(1); k < batch; k = (int)next.fetch_add(1)) {
       const uint32_t h = heights[k], w = widths[k], mode = modes[k];
       status[k] = 0;
       if (mode > 1) continue;
+      if (rmode && (h > (uint32_t)max_h || w > (uint32_t)max_w ||
+                    !resample_window_ok(crops[4 * k], crops[4 * k + 1], crops[4 * k + 2], crops[4 * k + 3], (int)h,
+                                        (int)w))) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "sample %d of %ux%u (at most %dx%d), window (%d, %d, %d, %d)", k, h, w, max_h,
+                 max_w, crops[4 * k], crops[4 * k + 1], crops[4 * k + 2], crops[4 * k + 3]);
+        std::fill(out + (uint64_t)k * out_stride, out + (uint64_t)k * out_stride + (uint64_t)out_h * out_w * 3,
+                  (uint8_t)0);
+        fail(k, buf);
+        continue;
+      }
       uint8_t *dst = out + (uint64_t)k * out_stride;
       const uint8_t *src = data[k];
       if (mode == 0) {
@@ -1072,7 +1087,9 @@ int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, con
         std::memcpy(dst, src, (size_t)h * w * 3);
         continue;
       }
-      if (crops) {
+      if (crops && rmode) {
+        resample_window_host(src, (int)w, crops + 4 * k, rmode, out_h, out_w, dst, rscr);
+      } else if (crops) {
         const int32_t *c = crops + 4 * k;
         resize(0, (int64_t)(uintptr_t)src, h, w, c[0], c[0] + c[2], c[1], c[1] + c[3], (int64_t)(uintptr_t)dst,
                out_h, out_w);
@@ -1081,6 +1098,36 @@ int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, con
   });
   if (err_k < batch) ffcv::set_error("sample %d: %s", err_k, err_msg.c_str());
   return FFCV_OK;
+}
+
+int ffcv_cpu_decode_batch(const uint8_t *const *data, const uint64_t *sizes, const uint32_t *heights,
+                          const uint32_t *widths, const uint32_t *modes, int batch, const int32_t *crops,
+                          int out_h, int out_w, uint8_t *out, uint64_t out_stride, int nthreads,
+                          int32_t *status) {
+  return cpu_decode_batch("ffcv_cpu_decode_batch", data, sizes, heights, widths, modes, batch, crops, 0, out_h, out_w,
+                          out, out_stride, 0, 0, nthreads, status);
+}
+
+// The crop decoders' 'bilinear' / 'bicubic' modes on the host:
+// the same loop with both resampling passes (resample_passes.h, the device's
+// records) in resize()'s place; a failed decode leaves zeros.  The shapes are
+// the device's: ffcv_jpeg_resample_fits(max_h, max_w, ...).
+int ffcv_cpu_decode_resample_batch(const uint8_t *const *data, const uint64_t *sizes, const uint32_t *heights,
+                                   const uint32_t *widths, const uint32_t *modes, int batch, const int32_t *crops,
+                                   int mode, int out_h, int out_w, uint8_t *out, uint64_t out_stride, int max_h,
+                                   int max_w, int nthreads, int32_t *status) {
+  const char *who = "ffcv_cpu_decode_resample_batch";
+  if (!crops || out_h <= 0 || out_w <= 0 || out_stride < (uint64_t)out_h * out_w * 3) {
+    ffcv::set_error("%s: invalid arguments", who);
+    return FFCV_EINVAL;
+  }
+  if (!ffcv_jpeg_resample_fits(max_h, max_w, out_h, out_w, mode)) {
+    ffcv::set_error("%s: images of up to %dx%d -> %dx%d, mode %d, are outside ffcv_jpeg_resample_fits", who, max_h,
+                    max_w, out_h, out_w, mode);
+    return FFCV_EINVAL;
+  }
+  return cpu_decode_batch(who, data, sizes, heights, widths, modes, batch, crops, mode, out_h, out_w, out, out_stride,
+                          max_h, max_w, nthreads, status);
 }
 
 // Measurement helper (bench.py's K1 lane-instructions per symbol): per

@@ -67,7 +67,8 @@
 // and the launches are below; the kernels are in the headers it includes, in
 // this order (jpeg_defs.h: tunables, the records between the kernels, wave
 // helpers; jpeg_entropy.h: K1 and k1_order_kernel; jpeg_idct.h: K1b;
-// jpeg_color_resize.h: K2 and k2_rec_kernel).
+// jpeg_color_resize.h: K2 and k2_rec_kernel; jpeg_color_resample.h: the
+// kernel that takes K2's place in the 'bilinear' / 'bicubic' modes).
 #include <climits>
 
 #include "api_internal.h"
@@ -75,6 +76,7 @@
 #include "jpeg_entropy.h"
 #include "jpeg_idct.h"
 #include "jpeg_color_resize.h"
+#include "jpeg_color_resample.h"
 
 // ---------------------------------------------------------------- ctx -----
 struct ffcv_jpeg_ctx {
@@ -376,7 +378,10 @@ static int arena_before_k1(ffcv_jpeg_ctx *c, JpegArgs &a, hipStream_t s) {
   return FFCV_OK;
 }
 
-static int launch_rrc(ffcv_jpeg_ctx *c, JpegArgs &a, hipStream_t s, const ffcv_rrc_params *p, void *out) {
+// rs: the launch of the 'bilinear' / 'bicubic' modes (jpeg_color_resample_kernel
+// in K2's place, on its own grid of bands), or null.
+static int launch_rrc(ffcv_jpeg_ctx *c, JpegArgs &a, hipStream_t s, const ffcv_rrc_params *p, void *out,
+                      const JpegResampleArgs *rs = nullptr) {
   const int batch = a.batch;
   a.p = *p;
   a.out = out;
@@ -431,7 +436,10 @@ static int launch_rrc(ffcv_jpeg_ctx *c, JpegArgs &a, hipStream_t s, const ffcv_r
   if (ev) FFCV_HIP_CHECK(hipEventRecord(ev[2], s));
   dim3 g2(nb, batch);
   if (!(only & 4)) {
-  } else if (fp16)
+  } else if (rs)
+    hipLaunchKernelGGL(jpeg_color_resample_kernel, dim3(rs->P.bands, batch), dim3(RESAMPLE_THREADS), rs->P.lds, s, a,
+                       *rs);
+  else if (fp16)
     hipLaunchKernelGGL((jpeg_color_resize_kernel<JM_RRC, true>), g2, dim3(K2T), K2_LDS, s, a);
   else
     hipLaunchKernelGGL((jpeg_color_resize_kernel<JM_RRC, false>), g2, dim3(K2T), K2_LDS, s, a);
@@ -491,6 +499,113 @@ int ffcv_jpeg_rrc_fused(ffcv_jpeg_ctx *c, void *stream, const uint8_t *base, con
   a.cut = a.cut_w = cutout_yx;
   a.flips = a.flips_w = flips;
   return launch_rrc(c, a, ffcv::as_stream(stream), p, out);
+}
+
+// ---- 'bilinear' / 'bicubic'  ------------------------------
+int ffcv_jpeg_resample_fits(int max_height, int max_width, int out_h, int out_w, int mode) {
+  BandResamplePlan P;
+  return band_resample_plan(max_height, max_width, out_h, out_w, mode, 0, 0, &P) ? 1 : 0;
+}
+
+// The mode, the output and the context's plan of a resample launch: what both
+// entries check before anything is launched.  *p: the launch's ffcv_rrc_params
+// (uint8 output, no epilogue).
+static int resample_params(const char *fn, ffcv_jpeg_ctx *c, int mode, int out_h, int out_w, uint64_t out_stride,
+                           int band_rows, int chunk_rows, ffcv_rrc_params *p, JpegResampleArgs *rs) {
+  if (mode != FFCV_RESAMPLE_BILINEAR && mode != FFCV_RESAMPLE_BICUBIC) {
+    ffcv::set_error("%s: mode %d (FFCV_RESAMPLE_BILINEAR or FFCV_RESAMPLE_BICUBIC)", fn, mode);
+    return FFCV_EINVAL;
+  }
+  if (out_h <= 0 || out_w <= 0 || band_rows < 0 || chunk_rows < 0) {
+    ffcv::set_error("%s: invalid params", fn);
+    return FFCV_EINVAL;
+  }
+  if (out_stride && out_stride < (uint64_t)out_h * out_w * 3) {
+    ffcv::set_error("%s: out_stride %llu for images of %llu bytes", fn, (unsigned long long)out_stride,
+                    (unsigned long long)out_h * out_w * 3);
+    return FFCV_EINVAL;
+  }
+  rs->mode = mode;
+  if (!band_resample_plan((int)c->max_h, (int)c->max_w, out_h, out_w, mode, band_rows, chunk_rows, &rs->P)) {
+    ffcv::set_error("%s: images of up to %ux%u -> %dx%d do not fit the %d bytes of LDS a workgroup may use "
+                    "(ffcv_jpeg_resample_fits)", fn, c->max_h, c->max_w, out_h, out_w, RESAMPLE_LDS_MAX);
+    return FFCV_EINVAL;
+  }
+  *p = ffcv_rrc_params{};
+  p->out_h = out_h;
+  p->out_w = out_w;
+  p->out_stride = out_stride;
+  return FFCV_OK;
+}
+
+static int resample_batch(const char *fn, ffcv_jpeg_ctx *c, void *stream, const uint8_t *base,
+                          const ffcv_sample *samples, int batch, const int32_t *crops, int mode, int out_h, int out_w,
+                          uint8_t *out, uint64_t out_stride, int32_t *status, int band_rows, int chunk_rows) {
+  int rc = check_common(fn, c, base, samples, batch, out, status);
+  if (rc) return rc;
+  if (!crops) {
+    ffcv::set_error("%s: invalid params", fn);
+    return FFCV_EINVAL;
+  }
+  ffcv_rrc_params p;
+  JpegResampleArgs rs;
+  if ((rc = resample_params(fn, c, mode, out_h, out_w, out_stride, band_rows, chunk_rows, &p, &rs))) return rc;
+  if (batch == 0) return FFCV_OK;
+  JpegArgs a = make_args(c, base, samples, batch, status);
+  a.crops = crops;
+  return launch_rrc(c, a, ffcv::as_stream(stream), &p, out, &rs);
+}
+
+int ffcv_jpeg_resample_batch(ffcv_jpeg_ctx *c, void *stream, const uint8_t *base, const ffcv_sample *samples,
+                             int batch, const int32_t *crops, int mode, int out_h, int out_w, uint8_t *out,
+                             uint64_t out_stride, int32_t *status) {
+  return resample_batch("ffcv_jpeg_resample_batch", c, stream, base, samples, batch, crops, mode, out_h, out_w, out,
+                        out_stride, status, 0, 0);
+}
+
+// Measurement hook (not in ffcv_hip.h): the launch with a given number of
+// output rows per band and window rows per chunk (0: the default of each).
+int ffcv_jpeg_resample_batch_plan(ffcv_jpeg_ctx *c, void *stream, const uint8_t *base, const ffcv_sample *samples,
+                                  int batch, const int32_t *crops, int mode, int out_h, int out_w, uint8_t *out,
+                                  uint64_t out_stride, int32_t *status, int band_rows, int chunk_rows) {
+  return resample_batch("ffcv_jpeg_resample_batch_plan", c, stream, base, samples, batch, crops, mode, out_h, out_w,
+                        out, out_stride, status, band_rows, chunk_rows);
+}
+
+int ffcv_jpeg_resample_fused(ffcv_jpeg_ctx *c, void *stream, const uint8_t *base, const ffcv_sample *table,
+                             uint64_t n_table, const uint64_t *ids, int batch, const ffcv_draw_params *dp,
+                             int32_t *crops, ffcv_sample *samples_out, int mode, int out_h, int out_w, uint8_t *out,
+                             uint64_t out_stride, int32_t *status) {
+  const char *fn = "ffcv_jpeg_resample_fused";
+  if (!c || !base || !table || !ids || !dp || !crops || !out || !status || batch < 0) {
+    ffcv::set_error("%s: invalid arguments", fn);
+    return FFCV_EINVAL;
+  }
+  if (batch > 65535) {  // as check_common
+    ffcv::set_error("%s: batch %d exceeds the 65535 images of one launch", fn, batch);
+    return FFCV_EINVAL;
+  }
+  if (batch > c->max_batch) {
+    ffcv::set_error("%s: batch %d exceeds ctx max_batch %d", fn, batch, c->max_batch);
+    return FFCV_EINVAL;
+  }
+  ffcv_rrc_params p;
+  JpegResampleArgs rs;
+  if (int rc = resample_params(fn, c, mode, out_h, out_w, out_stride, 0, 0, &p, &rs)) return rc;
+  if (dp->out_h != out_h || dp->out_w != out_w) {
+    ffcv::set_error("%s: draw and resize parameters disagree", fn);
+    return FFCV_EINVAL;
+  }
+  if (batch == 0) return FFCV_OK;
+  JpegArgs a = make_args(c, base, nullptr, batch, status);
+  a.table = table;
+  a.n_table = n_table;
+  a.ids = ids;
+  a.samples_out = samples_out;
+  a.dp = *dp;
+  a.do_draw = 1;
+  a.crops = a.crops_w = crops;
+  return launch_rrc(c, a, ffcv::as_stream(stream), &p, out, &rs);
 }
 
 int ffcv_jpeg_decode_batch(ffcv_jpeg_ctx *c, void *stream, const uint8_t *base, const ffcv_sample *samples,

@@ -265,9 +265,14 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
     """Abstract crop-then-resize decoder (rgb_image.py:142-217)."""
 
     crop_kind = 0
+    INTERPOLATIONS = ('area', 'bilinear', 'bicubic')
 
-    def __init__(self, output_size):
+    def __init__(self, output_size, interpolation='area'):
         super().__init__()
+        if not isinstance(interpolation, str) or interpolation not in self.INTERPOLATIONS:
+            raise ValueError(f'{type(self).__name__}: interpolation must be one of {self.INTERPOLATIONS}, '
+                             f'got {interpolation!r}')
+        self.interpolation = interpolation
         self.output_size = output_size
 
     # graph lowering hook: (cutout, flip, cutout_before_flip, normalize)
@@ -281,6 +286,15 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
         dev = _pipeline_device(self)
         output_shape = (int(self.output_size[0]), int(self.output_size[1]), 3)
         self._on_device = dev.type == 'cuda'
+        if self.interpolation != 'area':
+            from .. import libffcv as L
+            if not L.jpeg_resample_fits(self.max_height, self.max_width, output_shape[0], output_shape[1],
+                                        self.interpolation):
+                raise ValueError(f'{type(self).__name__}: interpolation={self.interpolation!r} from images of up to '
+                                 f'{int(self.max_height)}x{int(self.max_width)} to {output_shape[0]}x'
+                                 f'{output_shape[1]} needs more than the 64 KiB of LDS a workgroup may use '
+                                 '(ffcv_jpeg_resample_fits); images of up to 512x512 with square outputs of up to '
+                                 '256 always fit (RGBImageField(max_resolution=...))')
         if not self._on_device:  # rgb_image.py:151-166: output + full-image temp per sample
             u1 = np.dtype('<u1')
             return (replace(previous_state, jit_mode=True, shape=output_shape, dtype=u1),
@@ -317,6 +331,7 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
         mem_read = self.memory_read
         jpg = IMAGE_MODES['jpg']
         no_epilogue = Epilogue()  # host Cutout / flip run as their own operations
+        interpolation, max_h, max_w = self.interpolation, int(self.max_height), int(self.max_width)
 
         def decode(batch_indices, my_storage, metadata, storage_state):
             destination, temp_storage = my_storage
@@ -334,8 +349,12 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
             images = [mem_read(f['data_ptr'], storage_state) for f in fields]
             modes = np.where(fields['mode'] == jpg, 0, 1)
             dst = destination[:B]
-            status = L.cpu_decode_batch(images, fields['height'], fields['width'], modes, dst, crops,
-                                        nthreads=_host_threads())
+            if interpolation != 'area':
+                status = L.cpu_decode_resample_batch(images, fields['height'], fields['width'], modes, dst, crops,
+                                                     interpolation, max_h, max_w, nthreads=_host_threads())
+            else:
+                status = L.cpu_decode_batch(images, fields['height'], fields['width'], modes, dst, crops,
+                                            nthreads=_host_threads())
             _raise_failed(L, status, ids)
             return dst
         decode.is_parallel = True
@@ -346,6 +365,8 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
         if not getattr(self, '_on_device', True):
             return self._generate_code_host()
         f_ix = self._field_index
+        if self.interpolation != 'area':
+            return self._generate_code_resample(f_ix)
         ep = self._epilogue
         rp = ep.fill_rrc_params(L.RRCParams())
         cut, norm = ep.cutout, ep.normalize
@@ -392,6 +413,44 @@ class ResizedCropRGBImageDecoder(SimpleRGBImageDecoder, metaclass=ABCMeta):
             return out[:B]
         return decode
 
+    def _generate_code_resample(self, f_ix) -> Callable:
+        """'bilinear' / 'bicubic': the same draws, then Pillow's antialiased
+        resampling of the window in the resize's place (ffcv_jpeg_resample_* for
+        the JPEG samples, ffcv_resample_raw_batch for the raw ones); uint8, no
+        epilogue (the graph fuses nothing into the decoder in these modes)."""
+        from .. import libffcv as L
+        mode = self.interpolation
+        max_h, max_w = int(self.max_height), int(self.max_width)
+        draw_params, name = self._draw_params, type(self).__name__
+
+        def decode(batch_indices, storage, metadata, ss):
+            out, smp, crops, cyx, flips, status = storage
+            B = len(batch_indices)
+            stream = ss.stream
+            out_h, out_w = int(out.shape[1]), int(out.shape[2])
+            dp = draw_params(ss.loader_seed, ss.epoch, out_h, out_w)
+            stride = out[0].numel()
+            if ss.dataset.data is not None and ss.any_mode(f_ix, 0):
+                ss.jpeg_decoder(f_ix).resample_fused(ss.data, ss.sample_table(f_ix), ss.batch_ids, dp, crops, mode,
+                                                     out_h, out_w, out, stride, status, samples_out=smp,
+                                                     stream=stream)
+                ss.check_status(status[:B], name)
+                if ss.any_mode(f_ix, 1):
+                    L.resample_raw_batch(ss.data, smp[:B], B, crops, mode, out_h, out_w, out, stride, max_h, max_w,
+                                         stream)
+                return out[:B]
+            samples = ss.batch_samples(f_ix, smp)
+            L.draw_batch(ss.batch_ids, samples, dp, crops, None, None, None, stream)
+            if ss.any_mode(f_ix, 1):
+                L.resample_raw_batch(ss.data, samples, B, crops, mode, out_h, out_w, out, stride, max_h, max_w,
+                                     stream)
+            if ss.any_mode(f_ix, 0):
+                ss.jpeg_decoder(f_ix).resample(ss.data, samples, B, crops, mode, out_h, out_w, out, stride, status,
+                                               stream)
+                ss.check_status(status[:B], name)
+            return out[:B]
+        return decode
+
     @property
     @abstractmethod
     def get_crop_generator(self):
@@ -402,11 +461,13 @@ class RandomResizedCropRGBImageDecoder(ResizedCropRGBImageDecoder):
     """Random crop + resize (rgb_image.py:220-242): ``output_size`` is the
     (height, width) every crop is resized to; a crop's area is a fraction
     of the image drawn from ``scale`` and its width/height from ``ratio``
-    (log-uniform), torchvision's RandomResizedCrop rule (get_random_crop)."""
+    (log-uniform), torchvision's RandomResizedCrop rule (get_random_crop).
+    ``interpolation``: 'area' (cv::resize INTER_AREA, the reference's),
+    'bilinear' or 'bicubic' (Pillow's antialiased resize of the window, uint8)."""
     crop_kind = 0
 
-    def __init__(self, output_size, scale=(0.08, 1.0), ratio=(0.75, 4 / 3)):
-        super().__init__(output_size)
+    def __init__(self, output_size, scale=(0.08, 1.0), ratio=(0.75, 4 / 3), interpolation='area'):
+        super().__init__(output_size, interpolation)
         self.scale = scale
         self.ratio = ratio
         self.output_size = output_size
@@ -417,11 +478,12 @@ class RandomResizedCropRGBImageDecoder(ResizedCropRGBImageDecoder):
 
 
 class CenterCropRGBImageDecoder(ResizedCropRGBImageDecoder):
-    """Center crop + resize (rgb_image.py:245-265); ratio = crop / min side."""
+    """Center crop + resize (rgb_image.py:245-265); ratio = crop / min side;
+    ``interpolation`` as RandomResizedCropRGBImageDecoder's."""
     crop_kind = 1
 
-    def __init__(self, output_size, ratio):
-        super().__init__(output_size)
+    def __init__(self, output_size, ratio, interpolation='area'):
+        super().__init__(output_size, interpolation)
         self.scale = None
         self.ratio = ratio
 

@@ -166,6 +166,17 @@ _SIGS = {
     'ffcv_resample_images_batch_host': (c_int, [c_void_p, c_uint64, c_int, c_int, c_int, c_void_p, c_int, c_int,
                                                 c_int, c_void_p, c_uint64, c_void_p, c_int]),
     'ffcv_resample_fits': (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    'ffcv_jpeg_resample_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                         c_int, c_void_p, c_uint64, c_void_p]),
+    'ffcv_jpeg_resample_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_uint64,
+                                         c_void_p]),
+    'ffcv_jpeg_resample_fits': (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    'ffcv_resample_raw_batch': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                        c_uint64, c_int, c_int, c_void_p]),
+    'ffcv_cpu_decode_resample_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                               c_int, c_int, c_int, c_void_p, c_uint64, c_int, c_int, c_int,
+                                               c_void_p]),
     'ffcv_simple_aug_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
     'ffcv_color_jitter_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_int, c_double,
@@ -477,6 +488,29 @@ def cpu_decode_batch(images, heights, widths, modes, out: np.ndarray, crops=None
                                      out.ctypes.data, stride, int(max(1, nthreads)), status.ctypes.data)
     if rc != 0:
         raise RuntimeError('ffcv_cpu_decode_batch: ' + lib().ffcv_last_error().decode(errors='replace'))
+    return status
+
+
+def cpu_decode_resample_batch(images, heights, widths, modes, out: np.ndarray, crops, mode, max_h, max_w,
+                              nthreads=1):
+    """cpu_decode_batch with crops, resampled ('bilinear' / 'bicubic': Pillow's
+    img.crop(window).resize(...)) instead of resized
+    (ffcv_cpu_decode_resample_batch).  Returns the status array."""
+    B = len(images)
+    ptrs = np.array([im.ctypes.data if im is not None else 0 for im in images], np.uint64)
+    sizes = np.array([im.size if im is not None else 0 for im in images], np.uint64)
+    hs = np.ascontiguousarray(heights, np.uint32)
+    ws = np.ascontiguousarray(widths, np.uint32)
+    ms = np.ascontiguousarray(modes, np.uint32)
+    cr = np.ascontiguousarray(crops, np.int32)
+    status = np.zeros(B, np.int32)
+    if not out.flags['C_CONTIGUOUS'] or out.dtype != np.uint8 or out.ndim != 4 or cr.shape != (B, 4):
+        raise ValueError('cpu_decode_resample_batch: out must be C-contiguous uint8 (B, h, w, 3), crops (B, 4)')
+    _check(lib().ffcv_cpu_decode_resample_batch(
+        ptrs.ctypes.data, sizes.ctypes.data, hs.ctypes.data, ws.ctypes.data, ms.ctypes.data, B, cr.ctypes.data,
+        RESAMPLE_MODES[mode], int(out.shape[1]), int(out.shape[2]), out.ctypes.data, out[0].nbytes if B else
+        int(np.prod(out.shape[1:])), int(max_h), int(max_w), int(max(1, nthreads)), status.ctypes.data),
+        'ffcv_cpu_decode_resample_batch')
     return status
 
 
@@ -811,6 +845,21 @@ def resample_images_batch_host(inp: np.ndarray, crops, mode, out: np.ndarray, st
                                                  int(out[0].nbytes) if B else 0, _p(status), int(max(1, nthreads))),
            'ffcv_resample_images_batch_host')
     return out[:B]
+
+
+def jpeg_resample_fits(max_height, max_width, out_h, out_w, mode):
+    """Whether the crop decoders' 'bilinear' / 'bicubic' launches (JPEG, raw and
+    host) serve images of up to max_height x max_width at this output."""
+    return bool(lib().ffcv_jpeg_resample_fits(int(max_height), int(max_width), int(out_h), int(out_w),
+                                              RESAMPLE_MODES[mode]))
+
+
+def resample_raw_batch(base, samples, batch, crops, mode, out_h, out_w, out, out_stride, max_h, max_w, stream=None):
+    """The raw samples of a batch: Pillow's crop(window).resize(...) of each
+    sample's stored image (ffcv_resample_raw_batch); JPEG samples are skipped."""
+    _check(lib().ffcv_resample_raw_batch(_p(base), _p(samples), int(batch), _p(crops), RESAMPLE_MODES[mode],
+                                         int(out_h), int(out_w), _p(out), int(out_stride), int(max_h), int(max_w),
+                                         _stream(stream)), 'ffcv_resample_raw_batch')
 
 
 def simple_aug_batch(base, samples, batch, height, width, params: SimpleAugParams, flips, cutout_yx,
@@ -1990,6 +2039,21 @@ class JpegDecoder:
                                          ctypes.byref(draw), _p(crops), _p(cutout_yx), _p(flips),
                                          _p(samples_out), ctypes.byref(params), _p(out),
                                          _p(status)), 'ffcv_jpeg_rrc_fused')
+
+    def resample(self, base, samples, batch, crops, mode, out_h, out_w, out, out_stride, status, stream=None):
+        """decode / crop / Pillow 'bilinear' | 'bicubic' resample, uint8 (ffcv_jpeg_resample_batch)."""
+        _check(lib().ffcv_jpeg_resample_batch(self.handle, _stream(stream), _p(base), _p(samples), int(batch),
+                                              _p(crops), RESAMPLE_MODES[mode], int(out_h), int(out_w), _p(out),
+                                              int(out_stride), _p(status)), 'ffcv_jpeg_resample_batch')
+
+    def resample_fused(self, base, table, ids, draw: DrawParams, crops, mode, out_h, out_w, out, out_stride,
+                       status, samples_out=None, stream=None):
+        """gather + crop draws + decode / crop / resample (ffcv_jpeg_resample_fused)."""
+        _check(lib().ffcv_jpeg_resample_fused(self.handle, _stream(stream), _p(base), _p(table),
+                                              table.numel() // 32, _p(ids), int(ids.shape[0]), ctypes.byref(draw),
+                                              _p(crops), _p(samples_out), RESAMPLE_MODES[mode], int(out_h),
+                                              int(out_w), _p(out), int(out_stride), _p(status)),
+               'ffcv_jpeg_resample_fused')
 
     def decode(self, base, samples, batch, out, out_stride, status, stream=None):
         _check(lib().ffcv_jpeg_decode_batch(self.handle, _stream(stream), _p(base), _p(samples),

@@ -168,6 +168,8 @@ class Graph:
             if not chain or not isinstance(chain[0], ResizedCropRGBImageDecoder):
                 continue
             dec = chain[0]
+            if dec.interpolation != 'area':   # the resample launch applies no epilogue
+                continue
             cutout, flip, cut_before_flip, norm = self._scan_epilogue(chain[1:])
             dec.fuse(cutout=cutout, flip=flip, cutout_before_flip=cut_before_flip, normalize=norm)
         for chain in self._chains.values():

@@ -359,6 +359,59 @@ int ffcv_jpeg_rrc_fused(ffcv_jpeg_ctx *ctx, void *stream, const uint8_t *base,
                         ffcv_sample *samples_out, const ffcv_rrc_params *p,
                         void *out, int32_t *status);
 
+/* The crop decoders' 'bilinear' / 'bicubic' modes: ffcv_jpeg_rrc_batch /
+ * ffcv_jpeg_rrc_fused with Pillow's antialiased resampling in the resize's
+ * place and no epilogue.  Image k of `out` (uint8 HWC, out_stride bytes apart,
+ * 0 = dense) = PIL's img_k.crop(crops[k]).resize((out_w, out_h), mode) of the
+ * decoded image (libjpeg-turbo ifast + fancy upsampling), byte for byte, by
+ * the arithmetic of ffcv_resample_images_batch (mode: FFCV_RESAMPLE_BILINEAR /
+ * FFCV_RESAMPLE_BICUBIC; taps clamp at the window's edges).  The entropy and
+ * IDCT kernels run as for ffcv_jpeg_rrc_batch; one kernel of a workgroup per
+ * band of output rows then converts the window's plane rows to RGB in LDS a
+ * chunk at a time and rolls both passes over them (no workspace).  Same
+ * guards, statuses and zero-filled failed samples as ffcv_jpeg_rrc_batch /
+ * ffcv_jpeg_rrc_fused; raw samples are skipped (ffcv_resample_raw_batch).
+ * The shapes served are those of ffcv_jpeg_resample_fits (1 / 0) for the
+ * context's max_height and max_width: every max_height, max_width <= 512 with
+ * every square output of 1 .. 256 in both modes, and beyond that whatever
+ * fits a workgroup's 64 KiB of LDS; FFCV_EINVAL before any launch otherwise,
+ * and for another mode or an out_stride smaller than an image. */
+int ffcv_jpeg_resample_batch(ffcv_jpeg_ctx *ctx, void *stream,
+                             const uint8_t *base, const ffcv_sample *samples,
+                             int batch, const int32_t *crops, int mode,
+                             int out_h, int out_w, uint8_t *out,
+                             uint64_t out_stride, int32_t *status);
+int ffcv_jpeg_resample_fused(ffcv_jpeg_ctx *ctx, void *stream,
+                             const uint8_t *base, const ffcv_sample *table,
+                             uint64_t n_table, const uint64_t *ids, int batch,
+                             const ffcv_draw_params *dp, int32_t *crops,
+                             ffcv_sample *samples_out, int mode, int out_h,
+                             int out_w, uint8_t *out, uint64_t out_stride,
+                             int32_t *status);
+int ffcv_jpeg_resample_fits(int max_height, int max_width, int out_h,
+                            int out_w, int mode);
+/* The raw samples (mode 1) of the same batch, by the same band kernel with an
+ * aligned-word row loader: each image's address, height and width come from
+ * its ffcv_sample; samples of the other mode are skipped.  An invalid window,
+ * or a sample larger than max_h x max_w, yields zeros.  The same predicate. */
+int ffcv_resample_raw_batch(const uint8_t *base, const ffcv_sample *samples,
+                            int batch, const int32_t *crops, int mode,
+                            int out_h, int out_w, uint8_t *out,
+                            uint64_t out_stride, int max_h, int max_w,
+                            void *stream);
+/* The CPU decoders' twin: ffcv_cpu_decode_batch with crops, resampled by the
+ * same records instead of resized (imdecode, or the raw bytes, then both
+ * passes on the host over nthreads threads).  status[k] = 0 / -1. */
+int ffcv_cpu_decode_resample_batch(const uint8_t *const *data,
+                                   const uint64_t *sizes,
+                                   const uint32_t *heights,
+                                   const uint32_t *widths,
+                                   const uint32_t *modes, int batch,
+                                   const int32_t *crops, int mode, int out_h,
+                                   int out_w, uint8_t *out,
+                                   uint64_t out_stride, int max_h, int max_w,
+                                   int nthreads, int32_t *status);
+
 /* Entropy index: index[n_samples][64][3] uint32, zero-initialised and owned
  * by the caller (768 B per dataset sample).  With it attached, a
  * ffcv_jpeg_rrc_fused decode of dataset sample ids[k] that finds no record
