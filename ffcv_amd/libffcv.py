@@ -252,6 +252,19 @@ _SIGS = {
     'ffcv_affine_tile_cols': (c_uint64, []),
     'ffcv_affine_tile_lds': (c_uint64, []),
     'ffcv_affine_tile_bytes': (c_uint64, [c_int, c_int, c_int, c_void_p, c_int, c_int]),
+    'ffcv_perspective_draw_batch': (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_int,
+                                            c_int, c_void_p, c_void_p, c_void_p]),
+    'ffcv_perspective_draw_batch_host': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_double, c_double, c_int,
+                                                 c_int, c_void_p, c_void_p]),
+    'ffcv_perspective_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_uint64]),
+    'ffcv_perspective_batch_host': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_uint64, c_int]),
+    'ffcv_perspective_whole_bytes': (c_uint64, []),
+    'ffcv_perspective_tile_rows': (c_uint64, []),
+    'ffcv_perspective_tile_cols': (c_uint64, []),
+    'ffcv_perspective_tile_lds': (c_uint64, []),
+    'ffcv_perspective_tile_bytes': (c_uint64, [c_int, c_int, c_int, c_void_p, c_int, c_int]),
     'ffcv_mixup_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int]),
     'ffcv_mixup_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int,
                                       c_int]),
@@ -1599,6 +1612,76 @@ def affine_batch_host(src: np.ndarray, dst: np.ndarray, mode, fill, apply, coef,
     coef = _per_image('affine_batch_host', 'coef', coef, np.int64, B, 6)
     _check(lib().ffcv_affine_batch_host(_p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef), 0,
                                         int(max(1, nthreads))), 'ffcv_affine_batch_host')
+    return dst[:B]
+
+
+PERSPECTIVE_DIRECT = (1 << 64) - 1      # ffcv_perspective_tile_bytes: a corner pixel of the tile takes fill
+
+
+def perspective_draw_batch(ids, loader_seed, epoch, p, distortion_scale, height, width, apply, coef, status=None,
+                           stream=None):
+    """RandomPerspective's nine draws of the batch and their coefficients on
+    the device (op id 26): apply uint8[B], coef float64 (B, 9)."""
+    _check(lib().ffcv_perspective_draw_batch(_stream(stream), _p(ids), int(ids.shape[0]), _seed64(loader_seed),
+                                             int(epoch), float(p), float(distortion_scale), int(height), int(width),
+                                             _p(apply), _p(coef), _p(status)), 'ffcv_perspective_draw_batch')
+
+
+def perspective_draw_batch_host(ids, loader_seed, epoch, p, distortion_scale, height, width):
+    """The same draws on the host: (apply uint8 (B,), coef float64 (B, 9))."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    apply = np.empty(ids.size, np.uint8)
+    coef = np.empty((ids.size, 9), np.float64)
+    _check(lib().ffcv_perspective_draw_batch_host(_p(ids), int(ids.size), _seed64(loader_seed), int(epoch), float(p),
+                                                  float(distortion_scale), int(height), int(width), _p(apply),
+                                                  _p(coef)), 'ffcv_perspective_draw_batch_host')
+    return apply, coef
+
+
+def perspective_whole_bytes():
+    """3 * H * W of the largest image one workgroup of perspective_batch warps whole."""
+    return int(lib().ffcv_perspective_whole_bytes())
+
+
+def perspective_tile_shape():
+    """(rows, columns) of an output tile beyond the whole-image regime."""
+    return int(lib().ffcv_perspective_tile_rows()), int(lib().ffcv_perspective_tile_cols())
+
+
+def perspective_tile_lds():
+    """Bytes of staged source beyond which a tile reads global memory directly."""
+    return int(lib().ffcv_perspective_tile_lds())
+
+
+def perspective_tile_bytes(height, width, mode, coef, tile_row, tile_col):
+    """Bytes the kernel stages for one tile (0: it reads nothing;
+    PERSPECTIVE_DIRECT: one of its corner pixels takes fill)."""
+    q = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+    if q.shape != (9,):
+        raise TypeError('nine coefficients are required')
+    return int(lib().ffcv_perspective_tile_bytes(int(height), int(width), int(mode), _p(q), int(tile_row),
+                                                 int(tile_col)))
+
+
+def perspective_batch(src, dst, mode, fill, apply, coef, dst_stride=0, stream=None):
+    """Warp (apply[k] != 0) or copy each image of a dense device uint8
+    (B, H, W, 3) batch into ``dst`` (ffcv_perspective_batch): one launch, out
+    of place; apply device uint8 (B,), coef device float64 (B, 9)."""
+    B, H, W = _u8_batch_dims(src, 'perspective_batch')
+    f = fill_u8(fill)
+    _check(lib().ffcv_perspective_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply),
+                                        _p(coef), int(dst_stride)), 'ffcv_perspective_batch')
+    return dst
+
+
+def perspective_batch_host(src: np.ndarray, dst: np.ndarray, mode, fill, apply, coef, nthreads=1):
+    """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
+    B, H, W = _u8_out_of_place_dims(src, dst, 'perspective_batch_host')
+    f = fill_u8(fill)
+    apply = _per_image('perspective_batch_host', 'apply', apply, np.uint8, B)
+    coef = _per_image('perspective_batch_host', 'coef', coef, np.float64, B, 9)
+    _check(lib().ffcv_perspective_batch_host(_p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef), 0,
+                                             int(max(1, nthreads))), 'ffcv_perspective_batch_host')
     return dst[:B]
 
 

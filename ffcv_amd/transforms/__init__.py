@@ -9,6 +9,7 @@ from .sharpness import RandomAdjustSharpness
 from .auto_augment import TrivialAugmentWide, RandAugment, AugMix
 from .hue import RandomHue, RandomColorJitter
 from .affine import RandomAffine, RandomRotation
+from .perspective import RandomPerspective
 from .tone import RandomPosterize, RandomAutocontrast, RandomEqualize, RandomInvert
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .cutmix import ImageCutMix, LabelCutMix, ImageMixupCutMix, LabelMixupCutMix
@@ -25,7 +26,7 @@ __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
            'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomAdjustSharpness', 'RandomHue',
            'RandomColorJitter',
-           'RandomAffine', 'RandomRotation', 'TrivialAugmentWide', 'RandAugment', 'AugMix',
+           'RandomAffine', 'RandomRotation', 'RandomPerspective', 'TrivialAugmentWide', 'RandAugment', 'AugMix',
            'RandomPosterize', 'RandomAutocontrast', 'RandomEqualize', 'RandomInvert',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'ImageCutMix', 'LabelCutMix', 'ImageMixupCutMix',
            'LabelMixupCutMix', 'RandomErasing', 'Poison', 'ReplaceLabel']

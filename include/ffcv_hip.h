@@ -1017,6 +1017,104 @@ uint64_t ffcv_affine_tile_bytes(int height, int width, int mode,
                                 const int64_t *coef, int tile_row,
                                 int tile_col);
 
+/* ------------------------------------------------- projective warp ---- */
+/* RandomPerspective (the semantics are this project's own).
+ * Seeding contract op id: 26.
+ *
+ * The draws: nine values from one stream per sample, always all nine:
+ * apply = rand() < p, then eight integers, each lo + min(int(floor(rand() *
+ * (hi - lo + 1))), hi - lo), with bw = floor(d * (width / 2)), bh = floor(d *
+ * (height / 2)) in float64 (d = distortion_scale, the divisions by 2 floor):
+ *   x0 in [0, bw], y0 in [0, bh]                      (top left)
+ *   x1 in [width - 1 - bw, width - 1], y1 in [0, bh]   (top right)
+ *   x2 in [width - 1 - bw, width - 1], y2 in [height - 1 - bh, height - 1]
+ *   x3 in [0, bw], y3 in [height - 1 - bh, height - 1] (bottom left)
+ * where the image's corners land in the output.  With P0 .. P3 these points,
+ * a sample whose (P[i+1] - P[i]) x (P[i+2] - P[i+1]) is <= 0 for an i (exact
+ * integers, indices mod 4) is not applied and takes the identity.
+ * The coefficients, float64, every operation rounded on its own; integer sums
+ * of the eight values are exact:
+ *   dx1 = x1 - x2; dx2 = x3 - x2; sx = x0 - x1 + x2 - x3;  dy1, dy2, sy alike
+ *   g = (sy dx2 - sx dy2) / (dx2 dy1 - dx1 dy2)
+ *   h = (dy1 sx - dx1 sy) / (dx2 dy1 - dx1 dy2)
+ *   a = (x1 - x0) + g x1;  b = (x3 - x0) + h x3;  c = x0
+ *   d = (y1 - y0) + g y1;  e = (y3 - y0) + h y3;  f = y0
+ *   A = e - f h;  B = c h - b;  C = b f - c e
+ *   D = f g - d;  E = a - c g;  F = c d - a f
+ *   G = d h - e g;  Hh = b g - a h;  I = a e - b d
+ *   det = (a A + b D) + c G
+ *   coef[k] = (A (width - 1)) / det, (B (width - 1)) / det, (C (width - 1)) /
+ *             det, (D (height - 1)) / det, (E ..) / det, (F ..) / det,
+ *             G / det, Hh / det, I / det
+ * (Heckbert's unit-square-to-quadrilateral matrix, its adjugate, the rows
+ * scaled to the source rectangle, over the determinant); a det that is not a
+ * positive finite number gives the identity, not applied.  The image's own
+ * corners give 1 0 0 / 0 1 0 / 0 0 1 exactly.
+ *   height, width : 2 .. 32767;  p, distortion_scale in [0, 1]
+ *   apply : uint8[B];  coef : float64[B][9]
+ *   status : int32[B] or NULL (device entry only) */
+int ffcv_perspective_draw_batch(void *stream, const uint64_t *sample_ids,
+                                int batch, uint64_t loader_seed,
+                                uint64_t epoch, double p,
+                                double distortion_scale, int height, int width,
+                                uint8_t *apply, double *coef, int32_t *status);
+int ffcv_perspective_draw_batch_host(const uint64_t *sample_ids, int batch,
+                                     uint64_t loader_seed, uint64_t epoch,
+                                     double p, double distortion_scale,
+                                     int height, int width, uint8_t *apply,
+                                     double *coef);
+
+/* The warp of a dense device [B][height][width][3] uint8 batch, out of place,
+ * in ONE launch; image k is written at dst + k * dst_stride_bytes (0 = dense),
+ * warped by q = coef[k] where apply[k] != 0 and copied otherwise.  For output
+ * column c and row r, in float64, every operation rounded on its own:
+ *   nx = (q0 c + q1 r) + q2;  ny = (q3 c + q4 r) + q5;  den = (q6 c + q7 r) + q8
+ *   w = 1.0 / den (IEEE);  X = nx w;  Y = ny w
+ * The pixel is fill (a HOST array of three) unless den > 0 and X and Y are
+ * finite and below 65536 in magnitude; otherwise it is ffcv_affine_batch's
+ * integer sample (mode: FFCV_AFFINE_BILINEAR or FFCV_AFFINE_NEAREST) of
+ *   Xq = int64(floor(X * 65536));  Yq = int64(floor(Y * 65536))
+ * each tap tested on its own against the image.  Any byte alignment of src and
+ * dst; loads are 16-byte aligned chunks holding at least one byte of an image
+ * or single bytes of it; no byte outside dst's image ranges is written.
+ * While 3 * height * width <= ffcv_perspective_whole_bytes() a workgroup owns
+ * an image and stages it in LDS; larger images are cut into tiles of
+ * ffcv_perspective_tile_rows() x ffcv_perspective_tile_cols() outputs.  A tile
+ * with den > 0 on its four corner pixels stages the corners' bounding box in
+ * the source (widened by a pixel a side, and by bilinear's row and column)
+ * while that takes at most ffcv_perspective_tile_lds() bytes, and reads a tap
+ * outside the staged box from global memory; any other tile reads its taps
+ * from global memory.
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, sizes outside
+ * 2 .. 32767, 3 * height * width > 2^31 - 1, a mode other than the two, a
+ * dst_stride_bytes smaller than an image, or src and dst ranges that overlap
+ * (dst == src included). */
+int ffcv_perspective_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                           int batch, int height, int width, int mode,
+                           const uint8_t *fill, const uint8_t *apply,
+                           const double *coef, uint64_t dst_stride_bytes);
+/* The same on host memory over nthreads threads, compiled from the kernel's
+ * pixel function. */
+int ffcv_perspective_batch_host(const uint8_t *src, uint8_t *dst, int batch,
+                                int height, int width, int mode,
+                                const uint8_t *fill, const uint8_t *apply,
+                                const double *coef, uint64_t dst_stride_bytes,
+                                int nthreads);
+uint64_t ffcv_perspective_whole_bytes(void);
+uint64_t ffcv_perspective_tile_rows(void);
+uint64_t ffcv_perspective_tile_cols(void);
+uint64_t ffcv_perspective_tile_lds(void);
+/* The bytes the kernel stages for tile (tile_row, tile_col) of a height x
+ * width image under coef (a HOST array of nine) and mode, from the kernel's
+ * own footprint code: 0 for a tile that reads nothing (its box misses the
+ * image; invalid arguments), 2^64 - 1 for a tile with a corner pixel that
+ * takes fill by the rule above (den <= 0 among them).  The tile reads global
+ * memory directly when the value exceeds ffcv_perspective_tile_lds() (beyond
+ * the whole-image regime, where the value is the image's chunks). */
+uint64_t ffcv_perspective_tile_bytes(int height, int width, int mode,
+                                     const double *coef, int tile_row,
+                                     int tile_col);
+
 /* --------------------------------------------------------- mixup ------ */
 /* mixup.py: ImageMixup.  Sample i of a dense [n_samples][sample_elems] array
  * belongs to batch s = i / batch_size, of length min(batch_size, n_samples -
