@@ -21,12 +21,13 @@ SOURCES = ['ffcv_common.hip', 'ffcv_rrc.hip', 'ffcv_jpeg.hip', 'ffcv_host.hip', 
            'ffcv_blur.hip', 'ffcv_hue.hip', 'ffcv_affine.hip', 'ffcv_tone.hip', 'ffcv_standalone.hip',
            'ffcv_simple_aug.hip', 'ffcv_sharpness.hip', 'ffcv_policy.hip', 'ffcv_cutmix.hip',
            'ffcv_erase.hip', 'ffcv_randaugment.hip', 'ffcv_augmix.hip', 'ffcv_randaugment_large.hip',
-           'ffcv_augmix_large.hip', 'ffcv_resample.hip', 'ffcv_resample_raw.hip', 'ffcv_perspective.hip']
+           'ffcv_augmix_large.hip', 'ffcv_resample.hip', 'ffcv_resample_raw.hip', 'ffcv_perspective.hip',
+           'ffcv_elastic.hip']
 HEADERS = ['api_internal.h', 'device_common.h', 'diag_hooks.h', 'color_common.h', 'blur_common.h', 'hue_common.h',
            'affine_common.h', 'tone_common.h', 'poison_common.h', 'jpeg_defs.h', 'jpeg_entropy.h', 'jpeg_idct.h',
            'jpeg_color_resize.h', 'lds_stage.h', 'resize_out.h', 'sharpness_common.h', 'band_tiles.h',
            'erase_common.h', 'ra_slot.h', 'ral_slot.h', 'augmix_mix.h', 'resample_common.h', 'resample_passes.h',
-           'jpeg_color_resample.h', 'perspective_common.h']
+           'jpeg_color_resample.h', 'perspective_common.h', 'elastic_common.h']
 ARCH = os.environ.get('PYTORCH_ROCM_ARCH', 'gfx950').split(';')[0]
 
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-shared', '-std=c++17',

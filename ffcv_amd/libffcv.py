@@ -265,6 +265,16 @@ _SIGS = {
     'ffcv_perspective_tile_cols': (c_uint64, []),
     'ffcv_perspective_tile_lds': (c_uint64, []),
     'ffcv_perspective_tile_bytes': (c_uint64, [c_int, c_int, c_int, c_void_p, c_int, c_int]),
+    'ffcv_elastic_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_uint64, c_uint64, c_double, c_double, c_uint64]),
+    'ffcv_elastic_batch_host': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_uint64,
+                                        c_uint64, c_double, c_double, c_uint64, c_int]),
+    'ffcv_elastic_tile_rows': (c_uint64, []),
+    'ffcv_elastic_tile_cols': (c_uint64, []),
+    'ffcv_elastic_tile_lds': (c_uint64, []),
+    'ffcv_elastic_lds_bytes': (c_uint64, [c_int, c_int, c_double]),
+    'ffcv_elastic_tile_bytes': (c_uint64, [c_int, c_int, c_int, c_uint64, c_uint64, c_uint64, c_double, c_double,
+                                           c_int, c_int]),
     'ffcv_mixup_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int]),
     'ffcv_mixup_batch_host': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int,
                                       c_int]),
@@ -1682,6 +1692,53 @@ def perspective_batch_host(src: np.ndarray, dst: np.ndarray, mode, fill, apply, 
     coef = _per_image('perspective_batch_host', 'coef', coef, np.float64, B, 9)
     _check(lib().ffcv_perspective_batch_host(_p(src), _p(dst), B, H, W, int(mode), _p(f), _p(apply), _p(coef), 0,
                                              int(max(1, nthreads))), 'ffcv_perspective_batch_host')
+    return dst[:B]
+
+
+def elastic_tile_shape():
+    """(rows, columns) of the outputs one workgroup of elastic_batch owns."""
+    return int(lib().ffcv_elastic_tile_rows()), int(lib().ffcv_elastic_tile_cols())
+
+
+def elastic_tile_lds():
+    """Bytes of staged source beyond which a tile reads global memory directly."""
+    return int(lib().ffcv_elastic_tile_lds())
+
+
+def elastic_lds_bytes(height, width, sigma):
+    """Dynamic LDS bytes of a workgroup of elastic_batch."""
+    return int(lib().ffcv_elastic_lds_bytes(int(height), int(width), float(sigma)))
+
+
+def elastic_tile_bytes(height, width, mode, sample_id, loader_seed, epoch, alpha, sigma, tile_row, tile_col):
+    """Bytes the kernel stages for one tile of one sample's image (0: every tap misses the image)."""
+    return int(lib().ffcv_elastic_tile_bytes(int(height), int(width), int(mode), int(sample_id),
+                                             _seed64(loader_seed), int(epoch), float(alpha), float(sigma),
+                                             int(tile_row), int(tile_col)))
+
+
+def elastic_batch(src, dst, mode, fill, ids, loader_seed, epoch, alpha, sigma, dst_stride=0, stream=None):
+    """ElasticTransform of a dense device uint8 (B, H, W, 3) batch into ``dst``
+    (ffcv_elastic_batch): one launch, out of place; ids device int64 / uint64 (B,)."""
+    B, H, W = _u8_batch_dims(src, 'elastic_batch')
+    if int(ids.shape[0]) < B:
+        raise TypeError(f'elastic_batch: {B} sample ids are required')
+    f = fill_u8(fill)
+    _check(lib().ffcv_elastic_batch(_stream(stream), _p(src), _p(dst), B, H, W, int(mode), _p(f), _p(ids),
+                                    _seed64(loader_seed), int(epoch), float(alpha), float(sigma), int(dst_stride)),
+           'ffcv_elastic_batch')
+    return dst
+
+
+def elastic_batch_host(src: np.ndarray, dst: np.ndarray, mode, fill, ids, loader_seed, epoch, alpha, sigma,
+                       nthreads=1):
+    """The same on C-contiguous numpy uint8 (B, H, W, 3) arrays."""
+    B, H, W = _u8_out_of_place_dims(src, dst, 'elastic_batch_host')
+    f = fill_u8(fill)
+    ids = _per_image('elastic_batch_host', 'ids', ids, np.uint64, B)
+    _check(lib().ffcv_elastic_batch_host(_p(src), _p(dst), B, H, W, int(mode), _p(f), _p(ids), _seed64(loader_seed),
+                                         int(epoch), float(alpha), float(sigma), 0, int(max(1, nthreads))),
+           'ffcv_elastic_batch_host')
     return dst[:B]
 
 

@@ -10,6 +10,7 @@ from .auto_augment import TrivialAugmentWide, RandAugment, AugMix
 from .hue import RandomHue, RandomColorJitter
 from .affine import RandomAffine, RandomRotation
 from .perspective import RandomPerspective
+from .elastic import ElasticTransform
 from .tone import RandomPosterize, RandomAutocontrast, RandomEqualize, RandomInvert
 from .mixup import ImageMixup, LabelMixup, MixupToOneHot
 from .cutmix import ImageCutMix, LabelCutMix, ImageMixupCutMix, LabelMixupCutMix
@@ -26,7 +27,7 @@ __all__ = ['ToTensor', 'ToDevice', 'ToTorchImage', 'NormalizeImage', 'Convert', 
            'RandomBrightness', 'RandomContrast', 'RandomSaturation',
            'RandomGrayscale', 'RandomSolarization', 'GaussianBlur', 'RandomAdjustSharpness', 'RandomHue',
            'RandomColorJitter',
-           'RandomAffine', 'RandomRotation', 'RandomPerspective', 'TrivialAugmentWide', 'RandAugment', 'AugMix',
+           'RandomAffine', 'RandomRotation', 'RandomPerspective', 'ElasticTransform', 'TrivialAugmentWide', 'RandAugment', 'AugMix',
            'RandomPosterize', 'RandomAutocontrast', 'RandomEqualize', 'RandomInvert',
            'ImageMixup', 'LabelMixup', 'MixupToOneHot', 'ImageCutMix', 'LabelCutMix', 'ImageMixupCutMix',
            'LabelMixupCutMix', 'RandomErasing', 'Poison', 'ReplaceLabel']

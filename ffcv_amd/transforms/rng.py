@@ -18,7 +18,9 @@ transforms/erase.py), 23 rand augment (RandAugment: two draws per operation
 slot from one stream), 24 aug mix chains (AugMix: ten draws per chain from one
 stream), 25 aug mix weights (AugMix: the Beta and Dirichlet gammas, legacy
 RandomState.standard_gamma, a stream of varying length), 26 perspective
-(RandomPerspective: nine draws from one stream).  The device kernels use the same function
+(RandomPerspective: nine draws from one stream), 27 elastic noise (no MT19937:
+the full 64-bit hash is the sample's key into ElasticTransform's per-pixel
+noise, transforms/elastic.py).  The device kernels use the same function
 (csrc/device_common.h sample_seed).  The reference itself draws from numba's
 per-thread generators seeded from OS entropy (nondeterministic); see
 DESIGN.md "RNG contract".

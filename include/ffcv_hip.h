@@ -1115,6 +1115,63 @@ uint64_t ffcv_perspective_tile_bytes(int height, int width, int mode,
                                      const double *coef, int tile_row,
                                      int tile_col);
 
+/* ------------------------------------------------ elastic transform ---- */
+/* transforms/elastic.py: ElasticTransform of a dense device
+ * [B][height][width][3] uint8 batch, out of place, in ONE launch and with no
+ * draw launch; image k is written at dst + k * dst_stride_bytes (0 = dense).
+ * All integer arithmetic behind the weight table:
+ *   key = splitmix64(splitmix64(splitmix64(loader_seed ^ 27 << 56) ^ epoch) ^
+ *         sample_ids[k]), all 64 bits
+ *   noise of pixel (r, c), axis a (0 = x, 1 = y): e = 2 (r width + c) + a,
+ *     u = ((splitmix64(key ^ (e >> 2)) >> 16 (e & 3)) & 0xFFFF) - 32768
+ *   k = int(8 sigma + 1), plus 1 when even;  R = (k - 1) / 2
+ *   g_i = exp(-0.5 (i / sigma)^2), S the sum of g_|i| for i = -R .. R in that
+ *     order, w_i = floor(65536 g_i / S + 0.5) (float64, on the host), then w_0
+ *     changed so that the 2 R + 1 weights sum to 65536
+ *   reflect border: i < 0 -> -i, i >= n -> 2 (n - 1) - i
+ *   h16 = (sum_i w_|i| u(r, c + i) + 32768) >> 16;  v = sum_j w_|j| h16(r + j, c)
+ *   amp = floor(128 alpha + 0.5);  d = (amp v + 2^22) >> 23 (int64): Q16 pixels
+ *   X = (c << 16) + d_x;  Y = (r << 16) + d_y
+ * and the pixel is ffcv_affine_batch's integer sample (mode:
+ * FFCV_AFFINE_BILINEAR or FFCV_AFFINE_NEAREST) at (X, Y), each tap tested on
+ * its own against the image, fill (a HOST array of three) outside it.
+ * A workgroup owns a tile of ffcv_elastic_tile_rows() x
+ * ffcv_elastic_tile_cols() outputs, rebuilds the tile's field in LDS and
+ * stages the source box its own displacements reach while that takes at most
+ * ffcv_elastic_tile_lds() bytes; beyond that its taps come from global memory.
+ * Any byte alignment of src and dst; no byte outside dst's image ranges is
+ * written.
+ * FFCV_EINVAL, before any launch, for a null pointer, batch < 0, sizes outside
+ * 2 .. 32767, 3 * height * width > 2^31 - 1, a mode other than the two, sigma
+ * < 1, R > 64 or R > min(height, width) - 1, alpha outside [0, 4096], a
+ * dst_stride_bytes smaller than an image, or src and dst ranges that overlap. */
+int ffcv_elastic_batch(void *stream, const uint8_t *src, uint8_t *dst,
+                       int batch, int height, int width, int mode,
+                       const uint8_t *fill, const uint64_t *sample_ids,
+                       uint64_t loader_seed, uint64_t epoch, double alpha,
+                       double sigma, uint64_t dst_stride_bytes);
+/* The same on host memory (sample_ids included) over nthreads threads, from
+ * the kernel's own functions over whole planes. */
+int ffcv_elastic_batch_host(const uint8_t *src, uint8_t *dst, int batch,
+                            int height, int width, int mode,
+                            const uint8_t *fill, const uint64_t *sample_ids,
+                            uint64_t loader_seed, uint64_t epoch, double alpha,
+                            double sigma, uint64_t dst_stride_bytes,
+                            int nthreads);
+uint64_t ffcv_elastic_tile_rows(void);
+uint64_t ffcv_elastic_tile_cols(void);
+uint64_t ffcv_elastic_tile_lds(void);
+/* Dynamic LDS bytes of a workgroup for these images and sigma (0: invalid). */
+uint64_t ffcv_elastic_lds_bytes(int height, int width, double sigma);
+/* The bytes the kernel stages for tile (tile_row, tile_col) of sample_id's
+ * image, computed on the host from the kernel's own functions: 0 for a tile
+ * whose taps all miss the image (and for invalid arguments); the tile reads
+ * global memory directly when the value exceeds ffcv_elastic_tile_lds(). */
+uint64_t ffcv_elastic_tile_bytes(int height, int width, int mode,
+                                 uint64_t sample_id, uint64_t loader_seed,
+                                 uint64_t epoch, double alpha, double sigma,
+                                 int tile_row, int tile_col);
+
 /* --------------------------------------------------------- mixup ------ */
 /* mixup.py: ImageMixup.  Sample i of a dense [n_samples][sample_elems] array
  * belongs to batch s = i / batch_size, of length min(batch_size, n_samples -
